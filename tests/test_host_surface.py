@@ -16,7 +16,6 @@ from futuredet_amd import Config, lib
 from futuredet_amd.configs import centerpoint_config
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CFG = "/root/reference/configs/centerpoint"
 
 
 def _plain(v):
@@ -48,10 +47,26 @@ def test_config_builder_matches_parsed_reference_configs():
             assert _plain(c[k]) == g[fname][k], (fname, k)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference configs only exist in the build container")
-def test_reference_config_files_load_unchanged():
+def _write_config_module(path, recorded):
+    """A config module in the form of the reference's centerpoint configs: module-level imports (det3d.utils.config_tool among
+    them), class_names derived from tasks with itertools, a logger object inside the neck dict and the assigner's
+    out_size_factor computed by get_downsample_factor(model); every other value is the one recorded in configs.json."""
+    lines = ["import itertools", "import logging", "", "from det3d.utils.config_tool import get_downsample_factor", ""]
+    lines += ["%s = %r" % (k, v) for k, v in recorded.items()]
+    lines += ['class_names = list(itertools.chain(*[t["class_names"] for t in tasks]))',
+              'model["neck"]["logger"] = logging.getLogger("RPN")',
+              'assigner["out_size_factor"] = get_downsample_factor(model)']
+    path.write_text("\n".join(lines) + "\n")
+
+
+def test_reference_config_files_load_unchanged(tmp_path):
+    """Config.fromfile on config modules written from configs.json (the 10 centerpoint configs parsed from the reference's files):
+    every recorded section loads unchanged and builds the detector the file names."""
     g = json.load(open(os.path.join(REPO, "tests", "golden", "configs.json")))
-    files = sorted(glob.glob(os.path.join(REF_CFG, "*.py")))
+    assert len(g) == 10
+    for name in sorted(g):
+        _write_config_module(tmp_path / name, g[name])
+    files = sorted(glob.glob(os.path.join(str(tmp_path), "*.py")))
     assert len(files) == 10
     for f in files:
         cfg = Config.fromfile(f)
