@@ -3,7 +3,7 @@
 The reference's config FILES load unchanged through Config.fromfile (tests check that against the parsed
 fixtures in tests/golden/configs.json); those files are not part of this repository, so benchmarks and GPU
 tests build the same dictionaries here.  Values: configs/centerpoint/nusc_centerpoint_forecast_n0_detection.py
-:6-15 (flags), :32-73 (model), :88-103 (test_cfg), :160-166 (voxel_generator)."""
+:6-15 (flags), :32-73 (model), :88-103 (test_cfg), :160-166 (voxel_generator).  ``dcn_head`` sets model.bbox_head.dcn_head (False in every shipped config)."""
 import itertools
 import logging
 
@@ -20,7 +20,7 @@ VARIANTS = {
 
 
 def centerpoint_config(variant="forecast_n0", class_name="car", voxel_size=(0.075, 0.075, 0.2),
-                       pc_range=(-54, -54, -5.0, 54, 54, 3.0), max_voxel_num=(120000, 160000)):
+                       pc_range=(-54, -54, -5.0, 54, 54, 3.0), max_voxel_num=(120000, 160000), dcn_head=False):
     timesteps, dense, ff, bev = VARIANTS[variant]
     tasks = [dict(num_class=1, class_names=[class_name])]
     model = dict(
@@ -33,7 +33,7 @@ def centerpoint_config(variant="forecast_n0", class_name="car", voxel_size=(0.07
         bbox_head=dict(type="CenterHead", in_channels=sum([256, 256]), tasks=tasks, dataset="nuscenes", weight=0.25,
                        code_weights=[1.0] * 10 if dense else [1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 0.2, 0.2, 1.0, 1.0],
                        common_heads={"reg": (2, 2), "height": (1, 2), "dim": (3, 2), "rot": (2, 2), "vel": (2, 2)},
-                       share_conv_channel=64, dcn_head=False, timesteps=timesteps, two_stage=False, reverse=False,
+                       share_conv_channel=64, dcn_head=bool(dcn_head), timesteps=timesteps, two_stage=False, reverse=False,
                        sparse=False, dense=dense, bev_map=bev, forecast_feature=ff, classify=False, wide_head=False))
     osf = get_downsample_factor(model)
     test_cfg = dict(post_center_limit_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_per_img=500,

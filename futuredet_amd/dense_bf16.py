@@ -175,7 +175,9 @@ class HeadMaps(dict):
 
 
 class HeadPlan(object):
-    """CenterHead without bev_map: shared conv, then per task one fused first conv and one block-diagonal final conv.
+    """CenterHead: shared conv, then per task one fused first conv and one block-diagonal final conv.  A DCN task (dcn_head,
+    center_head.py:176-229) first runs its two FeatureAdaption modules as one fd_deform_adapt_nhwc launch into a [B,H,W,128]
+    buffer (cls adaption in channels 0-63, reg in 64-127); its cls_head joins the fused convs as the ``hm`` branch.
     With forecast_feature (n3dtf, center_head.py:119-124,383-386) each task first runs its two forecast convs; task
     i > 0 reads cat[x, feats_{i-1}], which is laid out in place: two ping-pong [B,H,W,2c] buffers hold x in channels
     [0,c) and receive the previous task's feats in [c,2c) (task 0 reads the same buffer through zero weights)."""
@@ -195,6 +197,7 @@ class HeadPlan(object):
             self.bev = [_Conv(w0, st[0].bias, 1, True, dtype)] + [_Conv(f.weight, f.bias, f.stride, f.relu, dtype) for f in st[1:]]
         self.ff = bool(head.forecast_feature)
         self.tasks = []
+        self.adapt = []  # per task: None, or the packed FeatureAdaption pair of a DCN task (hip_ops.pack_deform_adapt)
         self.pre = []
         for ti, task in enumerate(head.tasks):
             if self.ff:
@@ -204,15 +207,33 @@ class HeadPlan(object):
                 if ti == 0:  # reads [x | stale feats]: zero weights on the second half
                     w0 = torch.cat([w0, torch.zeros_like(w0)], dim=1)
                 self.pre.append((_Conv(w0, st[0].bias, 1, True, dtype), _Conv(st[1].weight, st[1].bias, 1, True, dtype)))
-            names = list(task.heads)
+            dcn = getattr(task, "task_head", None) is not None  # DCNSepHead (center_head.py:176-229)
+            sep = task.task_head if dcn else task
+            names = list(sep.heads)
+            stacks = [list(getattr(sep, h)._modules.values()) for h in names]
+            if dcn:  # hm last, as DCNSepHead.forward adds it after the task_head's maps
+                names.append("hm")
+                stacks.append(list(task.cls_head._modules.values()))
             firsts, finals = [], []
-            for h in names:
-                st = fold_stack(list(getattr(task, h)._modules.values()), torch.float32, False)
+            for mods in stacks:
+                st = fold_stack(mods, torch.float32, False)
                 assert len(st) == 2
                 firsts.append(st[0])
                 finals.append(st[1])
             w1 = torch.cat([f.weight for f in firsts], 0)
             b1 = torch.cat([f.bias for f in firsts], 0)
+            adapt = None
+            if dcn:
+                # one fd_deform_adapt_nhwc launch writes [cls | reg] adapted maps; the fused first conv reads all 128 channels through
+                # block weights: the task_head branches see channels 64-127 only, cls_head's first conv (the last 64 outputs) 0-63
+                fc, fr = task.feature_adapt_cls, task.feature_adapt_reg
+                adapt = hip_ops.pack_deform_adapt(fc.conv_adaption.weight, fr.conv_adaption.weight, fc.conv_offset.weight, fc.conv_offset.bias,
+                                                  fr.conv_offset.weight, fr.conv_offset.bias, dtype == torch.bfloat16)
+                cin = w1.shape[1]
+                n_hm = firsts[-1].weight.shape[0]
+                z = torch.zeros_like(w1)
+                w1 = torch.cat([torch.cat([z[:-n_hm], w1[:-n_hm]], 1), torch.cat([w1[-n_hm:], z[-n_hm:]], 1)], 0)
+                assert w1.shape[1] == 2 * cin
             hc = firsts[0].weight.shape[0]
             couts = [f.weight.shape[0] for f in finals]
             w2 = torch.zeros((sum(couts), hc * len(names), 3, 3), dtype=torch.float32, device=w1.device)
@@ -232,6 +253,7 @@ class HeadPlan(object):
             else:
                 c2 = _Conv(w2, b2, 1, False, dtype)
             self.tasks.append((_Conv(w1, b1, 1, True, dtype), c2, names, couts))
+            self.adapt.append(adapt)
 
     def __call__(self, x, bev_map=None):  # x [B,H,W,C] of the plan's dtype (bev_map [B,6,H,W]) -> list of HeadMaps
         if self.bev is not None:
@@ -281,7 +303,8 @@ class HeadPlan(object):
                 x = p1(p0(cat[ti & 1]))                             # feats_i, contiguous for this task's heads
                 cat[(ti + 1) & 1][..., hc:].copy_(x)                # and behind x for the next task's concat
                 d["feats"] = x.permute(0, 3, 1, 2)
-            y1 = c1(x)
+            adapt = self.adapt[ti]
+            y1 = c1(x if adapt is None else hip_ops.deform_adapt_nhwc(x, adapt[0], adapt[1], adapt[2]))
             uniform = all(tuple(t[3]) == tuple(self.tasks[0][3]) for t in self.tasks)
             if uniform:
                 if zbuf is None:  # all tasks have the same branch widths: one [T, B, H, W, C_total] buffer takes every task's final convs

@@ -7,8 +7,10 @@ per timestep), "dense" (n3dtf / n3dtfm: one task per timestep, optional chained 
 heat-map whose channel maximum is the score map); ``reverse`` (center_head.py:559: decoded exactly like the standard head -- the mode differs in
 the training targets only) and ``sparse`` (:322-324,572-587: a forward and a reverse task, each with a velocity pair per timestep; the forward
 task's steps first, then the reverse task's) and ``wide_head`` (:332-334,597-604: ONE task on a 512-channel shared convolution whose branches keep that
-width and whose heat-map has a channel per timestep; step s decodes channel s with the shared regression maps); ``dcn_head`` / ``two_stage`` are
-False in every shipped config and raise.  In eval mode on the device the head runs on the convolution plan of dense_bf16.py
+width and whose heat-map has a channel per timestep; step s decodes channel s with the shared regression maps); ``dcn_head`` (:176-229,358-372:
+each task a DCNSepHead -- two deformable FeatureAdaption modules, a cls_head for ``hm`` and a SepHead for the other maps -- on the one
+launch of fd_deform_adapt_nhwc) with every mode whose reference forward runs (not forecast_feature / wide_head, 64 shared channels);
+``two_stage`` is False in every shipped config and raises.  In eval mode on the device the head runs on the convolution plan of dense_bf16.py
 (the only device path; a head it cannot take raises); predict() runs the HIP decode + rotated NMS (fd_centerpoint_decode) for
 all (sample, heat-map) groups in one call; the loss is training-only and out of scope of this path.
 """
@@ -19,7 +21,7 @@ import torch
 from torch import nn
 
 from . import hip_ops
-from .nn_utils import Sequential, kaiming_init, weights_version
+from .nn_utils import Sequential, deform_conv2d_v1, kaiming_init, weights_version
 from .registry import HEADS
 
 
@@ -69,6 +71,58 @@ class SepHead(nn.Module):
         return self.forward_modules(x)
 
 
+class DeformConv(nn.Module):
+    """det3d/ops/dcn/deform_conv.py:192-240 as the reference builds it here: 3x3, stride 1, padding 1, no bias (``weight`` only)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, deformable_groups=4):
+        super().__init__()
+        self.padding, self.deformable_groups = padding, deformable_groups
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        n = in_channels * kernel_size * kernel_size  # deform_conv.py:225-230
+        stdv = 1.0 / n ** 0.5
+        self.weight.data.uniform_(-stdv, stdv)
+
+    def forward(self, x, offset):
+        return deform_conv2d_v1(x, offset, self.weight, self.deformable_groups, self.padding)
+
+
+class FeatureAdaption(nn.Module):
+    """center_head.py:40-78: ReLU(DeformConv(x, conv_offset(x))), conv_offset a 1x1 conv to dg * 2 * k * k offset channels (zero-initialised)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, deformable_groups=4):
+        super().__init__()
+        self.conv_offset = nn.Conv2d(in_channels, deformable_groups * kernel_size * kernel_size * 2, 1, bias=True)
+        self.conv_adaption = DeformConv(in_channels, out_channels, kernel_size=kernel_size, padding=(kernel_size - 1) // 2,
+                                        deformable_groups=deformable_groups)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv_offset.weight.data.zero_()
+
+    def forward(self, x):
+        return self.relu(self.conv_adaption(x, self.conv_offset(x)))
+
+
+class DCNSepHead(nn.Module):
+    """center_head.py:176-229: ``hm`` from cls_head on the cls adaption, the other maps from a SepHead on the reg adaption."""
+
+    def __init__(self, in_channels, num_cls, heads, head_conv=64, final_kernel=1, bn=False, init_bias=-2.19, **kwargs):
+        super().__init__(**kwargs)
+        self.feature_adapt_cls = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        self.feature_adapt_reg = FeatureAdaption(in_channels, in_channels, kernel_size=3, deformable_groups=4)
+        self.cls_head = Sequential(nn.Conv2d(in_channels, head_conv, kernel_size=3, padding=1, bias=True), nn.BatchNorm2d(64),
+                                   nn.ReLU(inplace=True),
+                                   nn.Conv2d(head_conv, num_cls, kernel_size=3, stride=1, padding=1, bias=True))
+        self.cls_head[-1].bias.data.fill_(init_bias)
+        self.task_head = SepHead(in_channels, heads, head_conv=head_conv, bn=bn, final_kernel=final_kernel)
+
+    def forward_modules(self, x):
+        ret = self.task_head(self.feature_adapt_reg(x))
+        ret["hm"] = self.cls_head(self.feature_adapt_cls(x))
+        return ret
+
+    def forward(self, x):
+        return self.forward_modules(x)
+
+
 def _drop_caches(module, incompatible_keys=None):
     module._plan = None
     module.__dict__.pop("_wv_tensors", None)
@@ -81,11 +135,17 @@ class CenterHead(nn.Module):
                  two_stage=False, reverse=False, sparse=False, dense=False, bev_map=False, forecast_feature=False,
                  classify=True, wide_head=False):
         super().__init__()
-        unsupported = dict(dcn_head=dcn_head, two_stage=two_stage)
-        on = [k for k, v in unsupported.items() if v]
-        if on:
-            raise NotImplementedError("CenterHead options %s are False in every shipped centerpoint config and are not "
-                                      "part of the inference hot path" % on)
+        if two_stage:
+            raise NotImplementedError("CenterHead option two_stage is False in every shipped centerpoint config and is not "
+                                      "part of the inference hot path")
+        if dcn_head:  # the combinations whose reference forward fails (64-channel FeatureAdaption / SepHead in DCNSepHead)
+            bad = [k for k, v in (("forecast_feature", forecast_feature), ("wide_head", wide_head)) if v]
+            if share_conv_channel != 64:
+                bad.append("share_conv_channel=%d" % share_conv_channel)
+            if bad:
+                raise ValueError("CenterHead(dcn_head=True): %s not supported -- the reference's DCNSepHead (center_head.py:176-229) "
+                                 "takes 64 shared channels only" % ", ".join(bad))
+        self.dcn_head = bool(dcn_head)
         self.two_stage, self.reverse, self.sparse, self.dense = two_stage, reverse, sparse, dense
         self.bev_map, self.forecast_feature, self.classify, self.wide_head = bev_map, forecast_feature, classify, wide_head
         self.target_timesteps = 7
@@ -125,6 +185,9 @@ class CenterHead(nn.Module):
             for head in heads.keys():
                 if not (self.dense or self.classify or self.wide_head) and head in ["vel", "rvel"]:  # center_head.py:355 (standard, reverse, sparse)
                     heads[head] = (self.timesteps * heads[head][0], heads[head][1])
+            if self.dcn_head:  # center_head.py:370-372: hm comes from the DCNSepHead's cls_head
+                self.tasks.append(DCNSepHead(share_conv_channel, num_cls, heads, bn=True, init_bias=init_bias, final_kernel=3))
+                continue
             heads.update(dict(hm=(num_cls, num_hm_conv)))
             cin = 2 * share_conv_channel if (i != 0 and self.forecast_feature) else share_conv_channel
             self.tasks.append(SepHead(cin, heads, bn=True, init_bias=init_bias, final_kernel=3, two_stage=self.two_stage,

@@ -528,6 +528,57 @@ def conv2d_wino_f32_num_tiles():
 CIRCLE_PRE_MAX = 4096  # candidates taken per group under circular NMS (the kernels' bound; the reference applies no cut there)
 
 
+def pack_deform_adapt(w_cls, w_reg, off_w_cls, off_b_cls, off_w_reg, off_b_reg, bf16):
+    """The two FeatureAdaption modules of a DCN task (conv_adaption weights [64, 64, 3, 3], conv_offset weights [72, 64, 1, 1] and
+    biases [72]) -> (packed conv_adaption weights for fd_deform_adapt_nhwc, off_w [2, 72, 64] fp32, off_b [2, 72] fp32), on the
+    device of w_cls.  The offset weights stay fp32 in the bf16 mode."""
+    L = _lib.load()
+    dev = w_cls.device
+    wc = w_cls.detach().to("cpu", torch.float32).contiguous()
+    wr = w_reg.detach().to("cpu", torch.float32).contiguous()
+    if tuple(wc.shape) != (64, 64, 3, 3) or tuple(wr.shape) != (64, 64, 3, 3):
+        raise FutureDetHipError("fd_deform_adapt: conv_adaption weights must be [64, 64, 3, 3], got %s / %s" % (tuple(wc.shape), tuple(wr.shape)))
+    host = torch.empty((L.fd_deform_adapt_packed_weight_bytes(int(bool(bf16))),), dtype=torch.uint8)
+    check(L.fd_deform_adapt_pack_weight(ctypes.c_void_p(wc.data_ptr()), ctypes.c_void_p(wr.data_ptr()), int(bool(bf16)),
+                                        ctypes.c_void_p(host.data_ptr())), "fd_deform_adapt_pack_weight")
+    ow = torch.stack([off_w_cls.detach().float().reshape(72, 64), off_w_reg.detach().float().reshape(72, 64)]).contiguous()
+    ob = torch.stack([off_b_cls.detach().float().reshape(72), off_b_reg.detach().float().reshape(72)]).contiguous()
+    return host.to(dev), ow.to(dev), ob.to(dev)
+
+
+def deform_adapt_nhwc(x, wpk, off_w=None, off_b=None, offsets=None, out=None):
+    """x [B,H,W,64] fp32 or bf16 -> [B,H,W,128] of x's dtype: ReLU(DCN_cls) in channels 0-63, ReLU(DCN_reg) in 64-127 (fd_deform_adapt_nhwc).
+    The offsets come from off_w / off_b (pack_deform_adapt; computed in the kernel) or, when given, from ``offsets`` [B,H,W,144] fp32."""
+    L = _lib.load()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise FutureDetHipError("x must be float32 or bfloat16, got %s" % (x.dtype,))
+    x = _dev(x, "x")
+    B, H, W, C = x.shape
+    bf16 = int(x.dtype == torch.bfloat16)
+    if offsets is not None:
+        _dev(offsets, "offsets", torch.float32)
+        if tuple(offsets.shape) != (B, H, W, 144):
+            raise FutureDetHipError("offsets must be [B, H, W, 144], got %s" % (tuple(offsets.shape),))
+    else:
+        if off_w is None or off_b is None:
+            raise FutureDetHipError("deform_adapt_nhwc: off_w and off_b are required without offsets")
+        _dev(off_w, "off_w", torch.float32)
+        _dev(off_b, "off_b", torch.float32)
+        if off_w.numel() != 2 * 72 * C or off_b.numel() != 2 * 72:
+            raise FutureDetHipError("off_w must be [2, 72, %d] and off_b [2, 72]" % C)
+    if wpk.numel() != L.fd_deform_adapt_packed_weight_bytes(bf16):
+        raise FutureDetHipError("deform_adapt_nhwc: packed weights are not of this dtype")
+    _dev(wpk, "wpk")
+    if out is None:
+        out = torch.empty((B, H, W, 2 * C), dtype=x.dtype, device=x.device)
+    _dev(out, "out", x.dtype)
+    if tuple(out.shape) != (B, H, W, 2 * C):
+        raise FutureDetHipError("out must be [B, H, W, %d], got %s" % (2 * C, tuple(out.shape)))
+    check(L.fd_deform_adapt_nhwc(_p(x), B, H, W, C, bf16, _p(off_w), _p(off_b), _p(offsets), _p(wpk), _p(out), _stream()),
+          "fd_deform_adapt_nhwc")
+    return out
+
+
 def make_decode_cfg(H, W, test_cfg, hm_channels=1, group_radius=None):
     """``hm_channels`` > 1: the score of a cell is the maximum over that many heat-map channels (CenterHead's ``classify``
     mode, center_head.py:589-595: torch.max(hm, dim=1) before the sigmoid).  ``group_radius``: test_cfg.circular_nms

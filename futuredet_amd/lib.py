@@ -123,6 +123,9 @@ SIGNATURES = {
     "fd_sweep_assemble_workspace_bytes": (c_size_t, [c_i64]),
     "fd_sweep_assemble": (c_int, [c_void_p, c_int, c_int, c_i64, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                   c_size_t, c_void_p]),
+    "fd_deform_adapt_packed_weight_bytes": (c_size_t, [c_int]),
+    "fd_deform_adapt_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "fd_deform_adapt_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -141,3 +141,46 @@ def fold_stack(modules, dtype, channels_last):
         out.append(FoldedConv(w, b.to(dtype) if b is not None else None, int(m.stride[0]), pad, relu, transposed))
         i = j
     return out
+
+
+def deform_conv2d_v1(x, offset, weight, deformable_groups=4, padding=1):
+    """DCN v1 (det3d/ops/dcn/deform_conv.py:192-240 with bias=False, stride 1, dilation 1) in torch, NCHW, any float dtype: the
+    torch restatement of fd_deform_adapt_nhwc for the eager / CPU path.  Sampling as in deform_conv_cuda_kernel.cu:85-117,191-240:
+    offset channel g * 2 k k + 2 (i k + j) is dh and + 1 is dw of group g (input channels [g C / dg, (g + 1) C / dg)); the sample at
+    h = y - pad + i + dh, w = x - pad + j + dw is 0 unless -1 < h < H and -1 < w < W, else the bilinear blend of the four corners
+    around it, a corner outside the map counting 0."""
+    B, C, H, W = x.shape
+    cout, cin, kh, kw = weight.shape
+    assert cin == C and C % deformable_groups == 0 and offset.shape == (B, deformable_groups * 2 * kh * kw, H, W)
+    dg, cpg = deformable_groups, C // deformable_groups
+    off = offset.to(x.dtype).view(B, dg, kh * kw, 2, H, W)
+    xg = x.reshape(B, dg, cpg, H * W)
+    ys = torch.arange(H, device=x.device).view(1, 1, H, 1)
+    xs = torch.arange(W, device=x.device).view(1, 1, 1, W)
+
+    def corner(yy, xx, ok):
+        idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).view(B, dg, 1, H * W).expand(B, dg, cpg, H * W)
+        v = torch.gather(xg, 3, idx).view(B, dg, cpg, H, W)
+        return torch.where(ok.unsqueeze(2), v, torch.zeros((), dtype=x.dtype, device=x.device))
+
+    cols = []
+    for i in range(kh):
+        for j in range(kw):
+            t = i * kw + j
+            h = (ys - padding + i).to(x.dtype) + off[:, :, t, 0]  # [B, dg, H, W]
+            w = (xs - padding + j).to(x.dtype) + off[:, :, t, 1]
+            inside = (h > -1) & (w > -1) & (h < H) & (w < W)
+            hf, wf = torch.floor(h), torch.floor(w)
+            lh, lw = h - hf, w - wf
+            hh, hw = 1 - lh, 1 - lw
+            hl = torch.where(inside, hf, torch.zeros_like(hf)).long()  # (outside the window the sample is 0 whatever h, w hold)
+            wl = torch.where(inside, wf, torch.zeros_like(wf)).long()
+            v1 = corner(hl, wl, (hl >= 0) & (wl >= 0))
+            v2 = corner(hl, wl + 1, (hl >= 0) & (wl + 1 <= W - 1))
+            v3 = corner(hl + 1, wl, (hl + 1 <= H - 1) & (wl >= 0))
+            v4 = corner(hl + 1, wl + 1, (hl + 1 <= H - 1) & (wl + 1 <= W - 1))
+            w1, w2, w3, w4 = [u.unsqueeze(2) for u in (hh * hw, hh * lw, lh * hw, lh * lw)]
+            val = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4
+            cols.append(torch.where(inside.unsqueeze(2), val, torch.zeros((), dtype=x.dtype, device=x.device)).reshape(B, C, H, W))
+    col = torch.stack(cols, 2)  # [B, C, k k, H, W]: column (c, tap) as the weight's [Cin, kh, kw] flattening
+    return torch.einsum("bckhw,ock->bohw", col, weight.to(x.dtype).reshape(cout, cin, kh * kw))

@@ -145,7 +145,7 @@ def seeded_state_dict(module, seed=0):
             v = rng.normal(0, 0.1, shape)
         elif leaf == "weight" and len(shape) == 1:  # norm scale
             v = rng.uniform(0.5, 1.5, shape)
-        elif key.endswith("hm.3.bias"):  # heat-map prior, init_bias=-2.19 (center_head.py:145-146)
+        elif key.endswith("hm.3.bias") or key.endswith("cls_head.3.bias"):  # heat-map prior, init_bias=-2.19 (center_head.py:145-146,212)
             v = np.full(shape, -2.19)
         elif leaf == "bias":
             v = rng.normal(0, 0.1, shape)

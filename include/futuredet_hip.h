@@ -442,6 +442,22 @@ int fd_rows_place(const uint64_t *words, const int32_t *prefix, int B, int D, in
                   const int32_t *n_dev, int64_t n_max, const float *src, int c_src, void *dst, int c_dst, int dst_bf16,
                   fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Deformable 3x3 convolution (DCN v1) of the CenterHead dcn_head option: the cls and the reg FeatureAdaption of one DCNSepHead
+ * in ONE launch (det3d/models/bbox_heads/center_head.py:40-78,176-229; module det3d/ops/dcn/deform_conv.py:192-240, arithmetic
+ * det3d/ops/dcn/src/deform_conv_cuda_kernel.cu:85-117,191-240).  Purely additive: fd_abi_version() stays 8.
+ * x [B,H,W,C] NHWC, C = 64, fp32 (bf16 = 0) or bf16 (bf16 = 1); y [B,H,W,128] of the same dtype: channels 0-63 =
+ * ReLU(DeformConv_cls(x, offset_cls)), 64-127 = ReLU(DeformConv_reg(x, offset_reg)); deformable groups 4, padding 1, no bias.
+ * Offsets are fp32 in both dtypes: either computed in the kernel from x by the 1x1 conv_offset of both branches (off_w
+ * [2][72][64] fp32 = [branch][offset channel][input channel], off_b [2][72]; `offsets` NULL) or read from `offsets` [B,H,W,144]
+ * fp32 (branch-major, the reference's channel order within a branch: group * 18 + 2 * tap + {0 = dh, 1 = dw}; off_w / off_b
+ * ignored).  Weights: fd_deform_adapt_pack_weight of the two [64, 64, 3, 3] conv_adaption weights (host buffers of
+ * fd_deform_adapt_packed_weight_bytes(bf16) bytes).  x, y and wpacked 16-byte aligned. */
+size_t fd_deform_adapt_packed_weight_bytes(int bf16);
+int fd_deform_adapt_pack_weight(const float *w_cls_oihw_host, const float *w_reg_oihw_host, int bf16, void *wpacked_host);
+int fd_deform_adapt_nhwc(const void *x, int B, int H, int W, int C, int bf16, const float *off_w, const float *off_b, const float *offsets,
+                         const void *wpacked, void *y, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
