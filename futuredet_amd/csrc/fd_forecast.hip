@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(1024) forecast_chains(FcArgs a) {
         a.fwd_idx += b * N * T; a.bwd_idx += b * N * T; a.fwd_ok += b * N; a.bwd_ok += b * N; a.match_idx += b * T * N;
         a.status += b; a.cv_centers += b * N * T * 3;
     }
-    if (tid < T) s_cnt[tid] = min(a.counts[tid], N);
+    if (tid < T) s_cnt[tid] = max(0, min(a.counts[tid], N));
     if (tid == 0) s_empty = 0;
     __syncthreads();
     if (tid < T && s_cnt[tid] == 0) s_empty = 1;  // tracker returns [] when any step is empty (nuscenes.py:150-158)
@@ -284,7 +284,7 @@ __global__ void __launch_bounds__(1024) forecast_traj_groups_kernel(const double
     const int tid = threadIdx.x;
     centers += b * T * N * 3; counts += b * T; fwd_ok += b * N; bwd_ok += b * N; bwd_idx += b * N * T; status += b;
     traj_kind += b * 3 * N; traj_src += b * 3 * N; traj_first += b * 3 * N; traj_group += b * 3 * N; n_traj += b;
-    const int n0 = status[0] ? 0 : min(counts[0], N), nl = status[0] ? 0 : min(counts[T - 1], N);
+    const int n0 = status[0] ? 0 : max(0, min(counts[0], N)), nl = status[0] ? 0 : max(0, min(counts[T - 1], N));
     // stable compaction of the two flag vectors (<= 256 entries each): thread 0 scans; the lists are tiny
     if (tid == 0) {
         int run = 0;

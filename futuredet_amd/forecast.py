@@ -248,7 +248,8 @@ def sweep_forecast(packed, counts, time, records=None, classname="car", out=None
     (``packed`` [B,T,post,11], ``counts`` [B,T], device tensors as CenterHead.predict / StaticStep return them) -> global-frame boxes ->
     chains -> trajectories and their forecast ids, all in HBM (hip_ops.ForecastOutputs; fd_forecast_from_detections, three launches,
     no synchronisation, capturable).  ``time`` [B,T-1] float64 and ``records`` [B,14] float64 (calibrated_sensor + ego_pose, see the
-    header) are device tensors: the devkit look-ups that produce them are the caller's (nuscenes.py:385-406)."""
+    header) are device tensors: the devkit look-ups that produce them are the caller's (nuscenes.py:385-406).  A step holds
+    min(count, post) boxes; a negative count (circular NMS's undecided group) is an empty step like 0: status 1, no trajectory."""
     reject = 2.0 if classname == "car" else 1.0  # nuscenes.py:126-132
     return hip_ops.forecast_from_detections(packed, counts, time, records, reject_thresh=reject, match_thresh=0.25, out=out)
 

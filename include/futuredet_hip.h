@@ -353,7 +353,8 @@ int fd_pillar_scatter(const void *feats, int c, int feat_stride, int dtype, cons
  *   bwd_idx [n_max, T], bwd_ok [n_max] : back-cast chain of last-step box i, hop s goes from step T-1-s to T-2-s (:222-237)
  *   match_idx [T, n_max]               : match_boxes: nearest step-t box to step-0 box i
  *   cv_centers [n_max, T, 3]           : constant-velocity forward trajectory of step-0 box i (:183-193)
- *   status int32[1]                    : 1 when some step has no box (the reference then returns no trajectory)
+ *   status int32[1]                    : 1 when some step has no box (the reference then returns no trajectory); a negative
+ *                                        count is an empty step
  * ------------------------------------------------------------------------------------------------- */
 int fd_forecast_chains(const double *centers, const double *velocity, const int32_t *counts, const double *time_dev, int T,
                        int n_max, double reject_thresh, int32_t *fwd_idx, int32_t *fwd_ok, int32_t *bwd_idx, int32_t *bwd_ok,
@@ -384,6 +385,8 @@ int fd_forecast_groups(const double *centers3, int n, double match_thresh, int32
  *                translation of every sample (the devkit look-ups of nuscenes.py:385-398 are the caller's); NULL = lidar frame.
  *                Device memory, because a captured graph is replayed for other samples: nothing of a sample is a kernel argument
  *   time_dev     [B][T-1] float64: seconds between consecutive forecast steps (get_time, nuscenes.py:399-406)
+ *   counts       [B][T] int32 in device memory: a step holds min(count, post) boxes.  A negative count (circular NMS's undecided
+ *                group, -1) is an empty step, like 0: status = 1, n_traj = 0, no trajectory of that sample
  *   out->center / quat / velocity [B,T,post,3|4|3] float64, size [B,T,post,3] float32: every slot's global-frame box
  *   out->fwd_idx ... status: fd_forecast_chains' outputs per sample ([B, ...] in front of the shapes documented there, n_max = post)
  *   out->traj_kind / traj_src / traj_first / traj_group [B, 3*post] int32, n_traj [B] (all five or none): the sweep's trajectories in

@@ -465,10 +465,9 @@ def gen_pillars():
     save("pillars.npz", **out)
 
 
-def gen_forecast():
-    """The reference's tracker / match_boxes (det3d/datasets/nuscenes/nuscenes.py:112-257) on seeded detections.  The
-    module's third-party imports (nuScenes devkit, shapely, pyquaternion, networkx) get inert shims; the boxes are plain
-    attribute holders (.center, .velocity, .tag) standing in for the devkit Box the functions only read those from."""
+def _import_nuscenes_module():
+    """det3d/datasets/nuscenes/nuscenes.py with inert shims for its third-party imports (nuScenes devkit, shapely, pyquaternion,
+    networkx -- the real networkx stays when it was imported first)."""
     import importlib
     mod = lambda name, **a: sys.modules.setdefault(name, type(sys)(name)).__dict__.update(a)
     mod("nuscenes"), mod("nuscenes.utils"), mod("nuscenes.utils.geometry_utils", view_points=None)
@@ -478,12 +477,22 @@ def gen_forecast():
         m = types.ModuleType("det3d.datasets")
         m.__path__ = [os.path.join(REF, "det3d", "datasets")]
         sys.modules["det3d.datasets"] = m
-    nm = importlib.import_module("det3d.datasets.nuscenes.nuscenes")
+    return importlib.import_module("det3d.datasets.nuscenes.nuscenes")
 
-    class B(object):
-        def __init__(self, c, v, tag):
-            self.center, self.velocity, self.tag = np.array(c, np.float64), np.array(v, np.float64), tag
 
+class _TagBox(object):
+    """Plain attribute holder (.center, .velocity, .tag) standing in for the devkit Box: tracker / match_boxes only read those."""
+
+    def __init__(self, c, v, tag):
+        self.center, self.velocity, self.tag = np.array(c, np.float64), np.array(v, np.float64), tag
+
+
+def gen_forecast():
+    """The reference's tracker / match_boxes (det3d/datasets/nuscenes/nuscenes.py:112-257) on seeded detections.  The
+    module's third-party imports (nuScenes devkit, shapely, pyquaternion, networkx) get inert shims; the boxes are plain
+    attribute holders (.center, .velocity, .tag) standing in for the devkit Box the functions only read those from."""
+    nm = _import_nuscenes_module()
+    B = _TagBox
     out = {}
     rng = np.random.default_rng(41)
     T = 7
@@ -512,6 +521,135 @@ def gen_forecast():
             out[case + "_match_tags"] = np.asarray([[b.tag[1] for b in row] for row in mb], np.int64)
         print("forecast", case, "trajectories", len(traj))
     save("forecast.npz", **out)
+
+
+def _edge_cases():
+    """The fixed case list of gen_forecast_edges: name -> (class, time [T-1], centres per step, velocities per step).  Every value is
+    float32-representable (the device path reads the boxes from float32 head rows), velocities have no z component (the head's velocity
+    triple is (vx, vy, 0)), and the tie / threshold cases use small integers and dyadics so that |a|^2 + |b|^2 - 2ab is exact or a
+    single correct rounding."""
+    rng = np.random.default_rng(43)
+    f32 = lambda a: np.asarray(a, np.float64).reshape(-1, 3).astype(np.float32).astype(np.float64)  # noqa: E731
+    cases = {}
+
+    def tracks(n0, T, counts, jitter, time, spread=40.0):
+        base = rng.uniform(-spread, spread, (n0, 3)) * [1, 1, 0.02]
+        vel = rng.normal(0, 3.0, (n0, 3)) * [1, 1, 0]
+        cs, vs = [], []
+        for t in range(T):
+            sel = rng.permutation(n0)[:min(n0, counts[t])]
+            extra = counts[t] - len(sel)
+            dt = float(np.sum(time[:t]))
+            cs.append(f32(np.concatenate([base[sel] + vel[sel] * dt + rng.normal(0, jitter, (len(sel), 3)) * [1, 1, 0],
+                                          rng.uniform(-spread, spread, (extra, 3)) * [1, 1, 0.02]])))
+            vs.append(f32(np.concatenate([vel[sel] + rng.normal(0, 0.3, (len(sel), 3)) * [1, 1, 0], rng.normal(0, 3.0, (extra, 3)) * [1, 1, 0]])))
+        return cs, vs
+
+    def rtime(T):
+        return 0.5 + rng.uniform(-0.02, 0.02, T - 1)
+
+    # ---- sizes: the smallest T with one box, the largest (T, post), ragged counts
+    t = rtime(2)
+    cases["one_t2"] = ("car", t) + tracks(1, 2, [1, 1], 0.3, t)
+    t = rtime(8)
+    c, v = tracks(256, 8, [256] * 8, 0.4, t, spread=60.0)
+    c[0][:24] = f32(np.array([[20.0 + 0.2 * i, -30.0, -1.0] for i in range(24)]))  # a 0.2 m chain of first boxes: one forecast group
+    cases["full_t8"] = ("car", t, c, v)
+    t = rtime(3)
+    cases["ragged_t3"] = ("pedestrian", t) + tracks(12, 3, [7, 12, 3], 0.2, t)
+    t = rtime(8)
+    cases["ragged_t8"] = ("car", t) + tracks(60, 8, [60, 1, 33, 59, 2, 60, 17, 40], 0.5, t)
+    # ---- an empty step at step 0, at an interior step and at step T-1
+    for T, cls in ((2, "car"), (8, "pedestrian")):
+        for e in sorted({0, T // 2, T - 1}):
+            counts = [int(rng.integers(3, 9)) for _ in range(T)]
+            counts[e] = 0
+            t = rtime(T)
+            cases["empty%d_t%d" % (e, T)] = (cls, t) + tracks(9, T, counts, 0.3, t)
+    # ---- exact reject thresholds (tm = 0.5, integer velocities): a hop of exactly 2.0 / 1.0 is kept (dis > reject is false), the next
+    #      float64 distance above it voids the chain.  Next above: a = (0,0), b = (r, q = 1.5 * 2^-26 * r): fl(r^2 + q^2) = r^2 + 2 ulp(r^2)
+    #      and its sqrt rounds to r + ulp(r) (checked with the reference's distance_matrix in gen_forecast_edges).
+    for cls, r in (("car", 2.0), ("pedestrian", 1.0)):
+        tag = "car" if cls == "car" else "ped"
+        h = 0.5
+        q = 1.5 * 2.0 ** -26 * r
+        # step 0: a box at rest at the origin, a moving box at (10,5) v (2,0), a far box
+        c0 = [[0, 0, -1], [10, 5, -1], [-30, 20, -1]]
+        v0 = [[0, 0, 0], [2, 0, 0], [0, 0, 0]]
+        # step 1: exactly r from both moved step-0 boxes; step 2: one hop of 0 and the far box
+        c1 = [[r, 0, -1], [11 + r, 5, -1], [-30, 20, -1]]
+        v1 = [[0, 0, 0], [2, 0, 0], [0, 0, 0]]
+        c2 = [[r, 0, -1], [12 + r, 5, -1], [-30, 20 + r, -1]]
+        v2 = [[0, 0, 0], [2, 0, 0], [0, 0, 0]]
+        cases["thr_%s_at" % tag] = (cls, np.array([h, h]), [f32(c0), f32(c1), f32(c2)], [f32(v0), f32(v1), f32(v2)])
+        c1 = [[r, q, -1], [-30, 20, -1]]
+        c2 = [[r, q, -1], [-30, 20 + r, -1]]
+        v1 = [[0, 0, 0], [0, 0, 0]]
+        cases["thr_%s_above" % tag] = (cls, np.array([h, h]), [f32([[0, 0, -1], [-30, 20, -1]]), f32(c1), f32(c2)], [f32(v1), f32(v1), f32(v1)])
+    # ---- exact ties: np.argmin keeps the first minimum
+    #      duplicated centres (forward hop, back-cast hop and match_boxes all see two identical candidates)
+    c0 = f32([[0, 0, -1], [20, 0, -1], [40, 8, -1]])
+    v0 = f32([[2, 0, 0], [0, 2, 0], [0, 0, 0]])
+    c1 = f32([[30, 30, -1], [1, 0, -1], [20, 1, -1], [1, 0, -1], [40, 8, -1], [20, 1, -1], [40, 8, -1]])
+    v1 = f32([[0, 0, 0], [2, 0, 0], [0, 2, 0], [2, 0, 0], [0, 0, 0], [0, 2, 0], [0, 0, 0]])
+    c2 = f32([[2, 0, -1], [20, 2, -1], [40, 8, -1], [2, 0, -1]])
+    v2 = f32([[2, 0, 0], [0, 2, 0], [0, 0, 0], [2, 0, 0]])
+    cases["tie_dup"] = ("car", np.array([0.5, 0.5]), [c0, c1, c2], [v0, v1, v2])
+    #      equidistant candidates: integer points symmetric about the moved centre, the nearer-looking one at the higher index
+    c0 = f32([[0, 0, -1], [10, 10, -1], [-10, 4, -1]])
+    v0 = f32([[2, 0, 0], [0, -2, 0], [0, 0, 0]])
+    # moved: (1,0), (10,9), (-10,4); candidates at distance 1 on either side, in both index orders
+    c1 = f32([[2, 0, -1], [0, 0, -1], [10, 8, -1], [10, 10, -1], [-9, 4, -1], [-10, 5, -1], [-11, 4, -1]])
+    v1 = f32([[0, 0, 0], [0, 0, 0], [0, 0, 0], [0, 0, 0], [0, 0, 0], [0, 0, 0], [0, 0, 0]])
+    # back-cast from step 2 (v = 0): each step-2 box is 1 from two step-1 boxes; match_boxes: step-0 boxes 1 from two step-2 boxes
+    c2 = f32([[1, 0, -1], [10, 9, -1], [-10, 4, -1], [0, 1, -1], [-1, 0, -1], [0, -1, -1], [11, 10, -1], [9, 10, -1]])
+    v2 = f32(np.zeros((8, 3)))
+    cases["tie_sym"] = ("pedestrian", np.array([0.5, 0.5]), [c0, c1, c2], [v0, v1, v2])
+    # ---- the match threshold of multi_future (0.25 m, strict): first boxes exactly 0.25 apart are not linked, 0.25 - 2^-26 apart
+    #      are (b = a + (0.25 - 2^-26, 0, 0) with a at the origin, so the square is exact)
+    d = 0.25 - 2.0 ** -26
+    c0 = f32([[0, 0, 0], [d, 0, 0], [1, 2, 0.5], [1.25, 2, 0.5], [1, 2.25, 0.5], [0, 0, 0.25], [3, 3, 0], [3.25, 3, 0], [3.5, 3, 0]])
+    v0 = f32(np.zeros((len(c0), 3)))
+    cases["ids_t2"] = ("car", np.array([0.5]), [c0, c0.copy()], [v0, v0.copy()])
+    return cases
+
+
+def gen_forecast_edges():
+    """The reference's tracker / match_boxes (nuscenes.py:112-257) and multi_future's grouping (:299-339) at the edges of the device
+    kernels' input range: T = 2 and 8, one box and 256 boxes per step, ragged counts, an empty step at the start, the middle and the
+    end, both classes (reject 2 m / 1 m), exact ties and exact thresholds.  Same shims and box holder as gen_forecast; networkx is the
+    real package (multi_future numbers the components)."""
+    import networkx  # noqa: F401  (the real one, before any inert shim can take its name)
+    nm = _import_nuscenes_module()
+    out = {}
+    cases = _edge_cases()
+    out["cases"] = np.array(list(cases))
+    for cls, r in (("car", 2.0), ("pedestrian", 1.0)):  # the threshold probes are what they claim to be
+        tag = "car" if cls == "car" else "ped"
+        for which, want in (("at", r), ("above", np.nextafter(r, 3.0))):
+            _, time, c, v = cases["thr_%s_%s" % (tag, which)]
+            assert nm.distance_matrix(c[0][:1, :2] + time[0] * v[0][:1, :2], c[1][:1, :2])[0, 0] == want
+            assert nm.distance_matrix(c[1][:1, :2] - time[0] * v[1][:1, :2], c[0][:1, :2])[0, 0] == want
+    for case, (cls, time, centers, velocity) in cases.items():
+        T = len(centers)
+        ret_boxes = [[_TagBox(centers[t][j], velocity[t][j], (t, j)) for j in range(len(centers[t]))] for t in range(T)]
+        for t in range(T):
+            out["%s_centers_%d" % (case, t)], out["%s_velocity_%d" % (case, t)] = centers[t].reshape(-1, 3), velocity[t].reshape(-1, 3)
+        out[case + "_class"] = np.array(cls)
+        out[case + "_time"] = np.asarray(time, np.float64)
+        traj = nm.tracker(cls, list(time), ret_boxes)
+        out[case + "_traj_tags"] = np.asarray([[b.tag[1] for b in tr] for tr in traj], np.int64).reshape(-1, T)
+        out[case + "_traj_centers"] = np.asarray([[b.center for b in tr] for tr in traj], np.float64).reshape(-1, T, 3)
+        # multi_future's forecast_id of every trajectory (translation = its first box's centre)
+        fb = {"tok": [{"translation": tr[0].center.tolist(), "detection_name": cls, "detection_score": 0.5, "forecast_score": 0.5,
+                       "forecast_id": -1, "forecast_boxes": []} for tr in traj]}
+        out[case + "_traj_ids"] = np.array([b["forecast_id"] for b in nm.multi_future(fb, cls)["tok"]], np.int64)
+        if all(len(b) for b in ret_boxes):
+            mb = nm.match_boxes(ret_boxes)
+            out[case + "_match_tags"] = np.asarray([[b.tag[1] for b in row] for row in mb], np.int64)
+        print("forecast_edges", case, "T", T, "counts", [len(b) for b in ret_boxes], "trajectories", len(traj),
+              "groups", len(set(out[case + "_traj_ids"].tolist())))
+    save("forecast_edges.npz", **out)
 
 
 class _Quaternion(object):
@@ -723,7 +861,8 @@ def gen_forecast2():
 if __name__ == "__main__":
     install_shims()
     sys.path.insert(0, REF)
-    which = sys.argv[1:] or ["voxelizer", "configs", "dense", "predict", "iou", "backbone", "sweeps", "pillars", "forecast", "forecast2"]
+    which = sys.argv[1:] or ["voxelizer", "configs", "dense", "predict", "iou", "backbone", "sweeps", "pillars", "forecast", "forecast2",
+                            "forecast_edges"]
     if len(which) > 1:
         # one generator per process: each installs the import shims it needs for the reference modules it imports, and the
         # shims of one (det3d.datasets stand-ins of the forecast generators) must not be what another finds in sys.modules
@@ -735,4 +874,4 @@ if __name__ == "__main__":
     for w in which:
         {"voxelizer": gen_voxelizer, "configs": gen_configs, "dense": gen_dense_nets, "predict": gen_predict,
          "iou": gen_iou, "backbone": gen_backbone, "sweeps": gen_sweeps, "pillars": gen_pillars, "forecast": gen_forecast,
-         "forecast2": gen_forecast2}[w]()
+         "forecast2": gen_forecast2, "forecast_edges": gen_forecast_edges}[w]()

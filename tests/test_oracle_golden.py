@@ -274,6 +274,41 @@ def test_oracle_forecast_tracker_matches_reference_golden(golden, case, cls):
         assert np.array_equal(np.asarray(ofc.match_indices(centers)), g[case + "_match_tags"])
 
 
+def test_oracle_forecast_edges_match_reference_golden(golden):
+    """oracle/forecast.py's tracker, match_indices and forecast_ids against the reference's tracker / match_boxes / multi_future at the
+    edges of the kernels' input range (forecast_edges.npz): T = 2 and 8, 1 and 256 boxes per step, ragged counts, an empty step first,
+    in the middle and last, both classes, exact ties (first index wins) and hops / first boxes exactly on the reject and match
+    thresholds and one float64 step above or below them.  Trajectory list, order, tags, centres and forecast ids exactly."""
+    from oracle import forecast as ofc
+
+    g = golden("forecast_edges.npz")
+    assert len(g["cases"]) >= 16
+    for case in g["cases"]:
+        T = 1 + len(g[case + "_time"])
+        centers = [g["%s_centers_%d" % (case, t)] for t in range(T)]
+        velocity = [g["%s_velocity_%d" % (case, t)] for t in range(T)]
+        res = ofc.tracker(str(g[case + "_class"]), list(g[case + "_time"]), centers, velocity)
+        want_tags, want_centers = g[case + "_traj_tags"], g[case + "_traj_centers"]
+        if res is None:
+            assert len(want_tags) == 0 and any(len(c) == 0 for c in centers), case
+            continue
+        assert len(want_tags) > 0, case
+        fwd, cv, bwd = res
+        tags = fwd + [[i] * T for i in range(len(centers[0]))] + bwd
+        assert np.array_equal(np.asarray(tags, np.int64).reshape(-1, T), want_tags), case
+        got_centers = [[centers[t][j] for t, j in enumerate(ch)] for ch in fwd] + [list(cv[i]) for i in range(len(cv))] + \
+                      [[centers[t][j] for t, j in enumerate(ch)] for ch in bwd]
+        assert np.array_equal(np.asarray(got_centers, np.float64).reshape(-1, T, 3), want_centers), case
+        assert np.array_equal(ofc.forecast_ids(want_centers[:, 0]), g[case + "_traj_ids"]), case
+        if case + "_match_tags" in g:
+            assert np.array_equal(np.asarray(ofc.match_indices(centers)), g[case + "_match_tags"]), case
+    # the cases reach what they are there for
+    assert len(g["thr_car_at_traj_tags"]) == 9 and len(g["thr_car_above_traj_tags"]) == 4
+    assert len(g["thr_ped_at_traj_tags"]) == 9 and len(g["thr_ped_above_traj_tags"]) == 4
+    assert len(set(g["ids_t2_traj_ids"].tolist())) == 8
+    assert len(g["full_t8_centers_0"]) == 256 and len(g["one_t2_centers_1"]) == 1
+
+
 def test_oracle_det_to_global_and_forecast_ids_match_reference_golden(golden):
     """oracle/forecast.py's array restatements of _second_det_to_nusc_box / _lidar_nusc_box_to_global / multi_future's
     grouping vs the reference's own functions (forecast2.npz; float64, 1e-12 relative -- BLAS vs plain summation order)."""
