@@ -24,9 +24,10 @@ int spconv_bf16_win_dispatch(const void *in, const void *wp_win, const float *bi
 int spconv_bf16_ws_dispatch(const void *in, const void *wp, const float *bias, const void *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
                             int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, void *out, hipStream_t stream);
 
-// fd_conv2d_wino_pc.hip: 0 = launched, 1 = shape not supported by the variant, -1 = dynamic LDS refused
+// fd_conv2d_wino_pc.hip: 0 = launched, 1 = shape not supported by the variant, -1 = dynamic LDS refused; wide_items: work items of 128
+// output channels (tile 8) instead of 64 (tile 7)
 int wino_pc_launch(const float *x, const void *wp, const float *bias, float *y, int B, int H, int W, int cin, int cout, int relu, int cout_total,
-                   int co_off, hipStream_t stream);
+                   int co_off, int wide_items, hipStream_t stream);
 
 // fd_spconv_f32r.hip: fp32, 16 input channels (weights resident in LDS, register accumulators, empty items skipped); 1 = launched
 int spconv_f32_res16_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride, int K,

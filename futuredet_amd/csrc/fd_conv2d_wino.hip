@@ -276,7 +276,7 @@ bool launch_wino(const float *x, const void *wp, const float *bias, float *y, Wi
     return true;
 }
 
-constexpr int kNumWinoTiles = 7;
+constexpr int kNumWinoTiles = 8;
 
 }  // namespace
 
@@ -343,12 +343,17 @@ extern "C" int fd_conv2d_wino_nhwc_f32(const float *x, int B, int H, int W, int 
         case 4: ok = launch_wino<8, 8, 1>(x, wpacked, bias, y, p, s); break;   // 16 x 16 pixels x 64 channels, 256
         case 5: ok = launch_wino<4, 4, 2>(x, wpacked, bias, y, p, s); break;   // 8 x 8 pixels x 128 channels, 128 (two workgroups per CU)
         case 7: {  // strips of 32 tiles x 64 channels, producer + consumer waves (fd_conv2d_wino_pc.hip); needs W >= 63
-            const int rc = fd::wino_pc_launch(x, wpacked, bias, y, B, H, W, cin, cout, relu, cout_total, co_off, s);
+            const int rc = fd::wino_pc_launch(x, wpacked, bias, y, B, H, W, cin, cout, relu, cout_total, co_off, 0, s);
             if (rc == 1) {
                 fd::set_error("fd_conv2d_wino_nhwc_f32: tile 7 needs W >= 63 and an input below 2 GB (got W = %d)", W);
                 return FD_EINVAL;
             }
             ok = rc == 0;
+            break;
+        }
+        case 8: {  // strips of 32 tiles x 128 channels (eight consumer waves); images narrower than one strip run tile 6's kernel
+            const int rc = fd::wino_pc_launch(x, wpacked, bias, y, B, H, W, cin, cout, relu, cout_total, co_off, 1, s);
+            ok = rc == 1 ? launch_wino<4, 4, 1>(x, wpacked, bias, y, p, s) : rc == 0;
             break;
         }
         default: ok = launch_wino<4, 4, 1>(x, wpacked, bias, y, p, s); break;  // 8 x 8 pixels x 64 channels, 64 (three per CU)

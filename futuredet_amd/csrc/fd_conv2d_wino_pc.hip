@@ -1,5 +1,6 @@
-// Winograd F(2x2, 3x3) in fp32 with producer and consumer waves (tile 7 of fd_conv2d_wino_nhwc_f32; same arithmetic, same
-// packed weights and bit-identical results as the kernels of fd_conv2d_wino.hip).
+// Winograd F(2x2, 3x3) in fp32 with producer and consumer waves (tiles 7 and 8 of fd_conv2d_wino_nhwc_f32; same arithmetic,
+// same packed weights and bit-identical results as the kernels of fd_conv2d_wino.hip).  What follows describes tile 7; tile 8 is
+// the same kernel with eight consumer waves and items of 128 output channels (see conv2d_wino_pc_f32 below).
 //
 // What bounds the one-role kernels (fd_conv2d_wino.hip, 49 % of the fp32 MFMA rate at best): a wave that owns 16 channels x 16
 // tiles needs one 1-KB weight fragment from L2 per 4 MFMAs (128 cycles); four SIMDs -> one vector-memory instruction per 32
@@ -51,6 +52,7 @@ struct PcParams {
     int tiles_x, tiles_y;
     unsigned x_bytes, w_bytes;
     int n_strips, n_items;
+    int nb_packed;  // 16-channel blocks of the packed weights (Cout rounded up to 64): blocks beyond re-read the last one
 };
 
 constexpr int NTB = 2, NTILE = 16 * NTB;        // tiles per workgroup
@@ -74,8 +76,15 @@ __device__ __forceinline__ f32x4 sub4(f32x4 a, f32x4 b) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 
-__global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restrict__ x, const float4 *__restrict__ wp, const float *__restrict__ bias,
-                                                          float *__restrict__ y, PcParams p) {
+// NCW consumer waves of 16 output channels each (a work item = 32 tiles x 16 NCW channels) + 4 producer waves.  NCW = 4: tile 7.
+// NCW = 8 (tile 8): one V of the producers feeds 128 output channels, so the input transform (VALU, which never co-issues with an
+// fp32 MFMA on its SIMD) and the barrier cost half as much per MFMA; 12 waves = 3 per SIMD leave 168 registers per wave, so the
+// consumers run one xi-step at a time (two accumulator chains each, the second consumer wave of the SIMD fills the gaps) with a
+// ring of 4 weight fragments requested 3 steps ahead.  Same MFMAs in the same order per accumulator: bit-identical to tile 7.
+template <int NCW>
+__global__ void __launch_bounds__(64 * (NCW + 4)) conv2d_wino_pc_f32(const float *__restrict__ x, const float4 *__restrict__ wp, const float *__restrict__ bias,
+                                                                   float *__restrict__ y, PcParams p) {
+    constexpr int NCT = 64 * NCW, CB = 16 * NCW;  // consumer threads, output channels per item
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // T[2] | V[2]
     unsigned char *s_t = smem, *s_v = smem + 2 * T_BYTES;
     float *s_bias = reinterpret_cast<float *>(smem + LDS_BYTES);  // [Cout_pad], zeros beyond Cout: a global load in the epilogue would
@@ -89,9 +98,9 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
     const int n_mine = (p.n_items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int G = n_mine * nslices;
 
-    if (wave >= 4) {
+    if (wave >= NCW) {
         // ------------------------------------------------------------------------------------------------ producers
-        const int pt = tid - 256;
+        const int pt = tid - NCT;
         const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(x), 0, (int)p.x_bytes, 0x00020000);
         const unsigned row_bytes = (unsigned)p.W * (unsigned)p.Cin * 4u;
         // A strip: tiles [t0, t0 + 32) = run 1 (n1 tiles from (b1, ty1, tx1), to the end of that tile row at most) + run 2 (the rest,
@@ -150,7 +159,7 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
         auto pass1 = [&](auto PAR, unsigned char *t) {
             constexpr int par = decltype(PAR)::value;
             pass1_item(st[par][0], t + p1o0);
-            if (wave == 4 && pt < N1 - 256) pass1_item(st[par][1], t + p1o1);
+            if (wave == NCW && pt < N1 - 256) pass1_item(st[par][1], t + p1o1);
         };
         // pass-2 item = (row r of T, tile, channel quad), quad and tile fastest: 16 lanes write 256 contiguous bytes of V and read
         // 4 tiles x 64 B of T at a stride of 128 / 192 B (the padding): conflict-free both ways.  Two items per thread; their LDS
@@ -221,7 +230,7 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
             body(P1{}, g + 1);  // (also when g + 1 == G: an idle step, matched by the consumers' extra barrier -- keeps both parities on every path)
         }
 #ifdef FD_V2_TRACE
-        if (tid == 256 && g_pctrace) { g_pctrace[(size_t)blockIdx.x * 8 + 3] = pacc[3]; g_pctrace[(size_t)blockIdx.x * 8 + 4] = pacc[4]; }
+        if (tid == NCT && g_pctrace) { g_pctrace[(size_t)blockIdx.x * 8 + 3] = pacc[3]; g_pctrace[(size_t)blockIdx.x * 8 + 4] = pacc[4]; }
 #endif
         return;
     }
@@ -240,20 +249,20 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
     // xi-steps (2p, 2p+1) the fragments of steps 2p+6, 2p+7 are requested into the slots the previous pair just released.
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(wp), 0, (int)p.w_bytes, 0x00020000);
     auto weights_of = [&](int item) {  // byte offset of the item's first fragment for this wave
-        const int nb = (item / p.n_strips) * 4 + wave;
-        return __builtin_amdgcn_readfirstlane((nb < (p.Cout_pad >> 4) ? nb : (p.Cout_pad >> 4) - 1) * total_steps * 1024);
+        const int nb = (item / p.n_strips) * NCW + wave;
+        return __builtin_amdgcn_readfirstlane((nb < p.nb_packed ? nb : p.nb_packed - 1) * total_steps * 1024);
     };
     const unsigned lane16 = lane * 16;
     auto fragment = [&](int base, int step) {
         return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, base + step * 1024, 0));
     };
-    constexpr int RW = 8, AHEAD = 6;
+    constexpr int RW = NCW == 4 ? 8 : 4, AHEAD = NCW == 4 ? 6 : 3;
     float4 bw[RW];
     int wb = weights_of((int)blockIdx.x);
 #pragma unroll
     for (int r = 0; r < AHEAD; ++r) bw[r] = fragment(wb, r);  // (total_steps >= 16)
     const bool wide = ((p.cout_total | p.co_off) & 3) == 0;
-    for (int c = tid; c < p.Cout_pad; c += 256) s_bias[c] = (bias && c < p.Cout_real) ? bias[c] : 0.f;
+    for (int c = tid; c < p.Cout_pad; c += NCT) s_bias[c] = (bias && c < p.Cout_real) ? bias[c] : 0.f;
     __syncthreads();
     __syncthreads();
     FD_PT(tpro);
@@ -262,7 +271,7 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
     for (int k = 0; k < n_mine; ++k) {
         const int item = (int)blockIdx.x + k * (int)gridDim.x;
         const int wnext = k + 1 < n_mine ? weights_of(item + (int)gridDim.x) : wb;  // the ring runs into the next item's fragments
-        const int co = (item / p.n_strips) * 64 + wave * 16 + lq * 4;
+        const int co = (item / p.n_strips) * CB + wave * 16 + lq * 4;
         f32x4 acc[16][NTB];
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi)
@@ -271,6 +280,7 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
         for (int s = 0; s < nslices; ++s, ++g) {
             const unsigned char *v = s_v + (g & 1) * V_BYTES;
             FD_PT(c0);
+            if constexpr (NCW == 4) {
             // Two xi-steps at a time: four independent accumulator chains (xi, tile block) are interleaved, so an MFMA's
             // accumulator was written four MFMAs (128 cycles) earlier.  An MFMA occupies the pipe for 32 cycles but issues in 4:
             // the V-fragment reads of the next pair and the weight requests are placed BETWEEN the groups of four MFMAs (fences),
@@ -312,6 +322,34 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
                 FD_KSTEP(w)
 #undef FD_KSTEP
             }
+            } else {
+            // one xi-step at a time, the four k-quarters of one tile block back to back (the other consumer wave of the SIMD
+            // fills the accumulation latency): a tile block's V fragment of the next step is read as soon as its last MFMA has
+            // issued; the weight fragment of step + 3 is requested at the start of the step, into the slot the previous step
+            // has just released (requested after this step's MFMAs: 1-2 % slower; 2 steps ahead: 6 % slower on 128->128; a
+            // deeper ring does not fit the 168 registers, a 5-slot ring with one unrolled body per phase spills)
+            float4 a[NTB];
+#pragma unroll
+            for (int i = 0; i < NTB; ++i) a[i] = *reinterpret_cast<const float4 *>(v + vbase + i * 16 * 64);
+#pragma unroll
+            for (int xi = 0; xi < 16; ++xi) {
+                const int step = s * 16 + xi;
+                {
+                    const int ns = step + AHEAD;
+                    bw[(xi + AHEAD) % RW] = ns < total_steps ? fragment(wb, ns) : fragment(wnext, ns - total_steps);
+                }
+#pragma unroll
+                for (int i = 0; i < NTB; ++i) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[xi][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[xi % RW].x, a[i].x, acc[xi][i], 0, 0, 0);
+                    acc[xi][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[xi % RW].y, a[i].y, acc[xi][i], 0, 0, 0);
+                    acc[xi][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[xi % RW].z, a[i].z, acc[xi][i], 0, 0, 0);
+                    acc[xi][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[xi % RW].w, a[i].w, acc[xi][i], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (xi + 1 < 16) a[i] = *reinterpret_cast<const float4 *>(v + vbase + ((xi + 1) * NTILE + i * 16) * 64);
+                }
+            }
+            }
             __builtin_amdgcn_sched_barrier(0);
             FD_PT(c1);
             __syncthreads();
@@ -335,7 +373,7 @@ __global__ void __launch_bounds__(512) conv2d_wino_pc_f32(const float *__restric
         // straight-line stores when nothing of the item can fall outside (every tile of the strip exists, no partial tile at the
         // right / bottom edge, the 64 channels exist, 16-byte aligned channel runs): true for all but the last strip of the RPN /
         // head layers.  The general form below has one exec-masked branch per store.
-        const bool interior = wide && n1 + n2 == NTILE && !((p.H | p.W) & 1) && (item / p.n_strips) * 64 + 64 <= p.Cout_real;
+        const bool interior = wide && n1 + n2 == NTILE && !((p.H | p.W) & 1) && (item / p.n_strips) * CB + CB <= p.Cout_real;
 #pragma unroll
         for (int i = 0; i < NTB; ++i) {
             const int j = i * 16 + lm;
@@ -407,23 +445,26 @@ namespace fd {
 
 // 0 = launched, 1 = shape not supported by this variant (narrower than one strip, or an input / weight tensor of 2 GB and more), -1 = LDS refused
 int wino_pc_launch(const float *x, const void *wp, const float *bias, float *y, int B, int H, int W, int cin, int cout, int relu, int cout_total,
-                   int co_off, hipStream_t stream) {
+                   int co_off, int wide_items, hipStream_t stream) {
+    const int cb = wide_items ? 128 : 64;  // output channels per work item
     PcParams p;
     p.B = B; p.H = H; p.W = W; p.Cin = cin;
     p.Cout_real = cout;
-    p.Cout_pad = (cout + 63) / 64 * 64;
+    p.Cout_pad = (cout + cb - 1) / cb * cb;
+    p.nb_packed = (cout + 63) / 64 * 4;
     p.cout_total = cout_total; p.co_off = co_off; p.relu = relu;
     p.tiles_x = (W + 1) / 2;
     p.tiles_y = (H + 1) / 2;
     const int64_t xb = (int64_t)B * H * W * cin * 4;
-    const int64_t wbytes = (int64_t)p.Cout_pad * cin * 16 * 4;
+    const int64_t wbytes = (int64_t)p.nb_packed * 16 * cin * 16 * 4;
     if (p.tiles_x < NTILE || xb >= 0x80000000ll || wbytes >= 0x80000000ll || p.Cout_pad > kMaxBias) return 1;
     p.x_bytes = (unsigned)xb;
     p.w_bytes = (unsigned)wbytes;
-    static std::atomic<uint64_t> lds_set{0};
+    static std::atomic<uint64_t> lds_set4{0}, lds_set8{0};
     const size_t lds = (size_t)LDS_BYTES + (size_t)p.Cout_pad * 4;
-    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(conv2d_wino_pc_f32), (size_t)LDS_BYTES + kMaxBias * 4, lds_set)) return -1;  // (the limit, once per device)
-    const int64_t n_strips = ((int64_t)p.tiles_x * p.tiles_y * B + NTILE - 1) / NTILE, n_items = n_strips * ((cout + 63) / 64);
+    const void *kern = wide_items ? reinterpret_cast<const void *>(conv2d_wino_pc_f32<8>) : reinterpret_cast<const void *>(conv2d_wino_pc_f32<4>);
+    if (!fd::ensure_dynamic_lds(kern, (size_t)LDS_BYTES + kMaxBias * 4, wide_items ? lds_set8 : lds_set4)) return -1;  // (the limit, once per device)
+    const int64_t n_strips = ((int64_t)p.tiles_x * p.tiles_y * B + NTILE - 1) / NTILE, n_items = n_strips * ((cout + cb - 1) / cb);
     if (n_items >= (1ll << 31)) return 1;
     p.n_strips = (int)n_strips;
     p.n_items = (int)n_items;
@@ -431,7 +472,8 @@ int wino_pc_launch(const float *x, const void *wp, const float *bias, float *y, 
     const int n_cu = fd::device_cu_count();
     const int rounds = (int)((n_items + n_cu - 1) / n_cu);
     const unsigned grid = (unsigned)((n_items + rounds - 1) / rounds);
-    hipLaunchKernelGGL(conv2d_wino_pc_f32, dim3(grid), dim3(512), lds, stream, x, (const float4 *)wp, bias, y, p);
+    if (wide_items) hipLaunchKernelGGL(conv2d_wino_pc_f32<8>, dim3(grid), dim3(768), lds, stream, x, (const float4 *)wp, bias, y, p);
+    else hipLaunchKernelGGL(conv2d_wino_pc_f32<4>, dim3(grid), dim3(512), lds, stream, x, (const float4 *)wp, bias, y, p);
     return 0;
 }
 
