@@ -20,12 +20,17 @@ rank-strided like DistributedSampler(shuffle=False) and run in micro-batches of 
 all ranks through one fixed-shape all_gather inside the timed region: after the last step in the weak-scaling mode (as the
 reference's eval loop does), per step in the strong-scaling mode.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed repetitions, --dump / --dump-outputs, the JSON line.
+Everything else in the list below -- the host-to-host and latency legs, the roofline, the CPU baseline and parity, the full
+pipeline's stage timings and the other workloads under "also" -- is measured only with --full (their keys are then null or absent).
+
 Rank 0 prints ONE JSON line.  Every number in it is either measured in this run or carries its provenance:
   value              sweeps/s, clouds resident in HBM when the clock starts -> detections on the host (the bench contract's
                      definition of `value`): the MEDIAN of --reps (5) repetitions of the K-step timed region, each with its own
                      barrier + synchronize + clock; `repetitions` carries min / median / max and every repetition's ms_per_step.
                      The LAST (R - 1) // 2 repetitions carry the instrumented step of the roofline measurement (an eager pass run
-                     alone: 1.6 % of a 20-step fp32 region, 5.3 % of a bf16 one), so the median repetition is one without it
+                     alone: 1.6 % of a 20-step fp32 region, 5.3 % of a bf16 one), so the median repetition is one without it.
+                     The timed region is the same program with or without --full
   value_host_to_host the same K steps with every cloud starting in pinned host memory (H2D inside the timed region):
                      SURVEY 8(d)'s "points on host -> boxes on host"
   latency_ms_inflight1  a third leg with ONE pass in flight: a sweep's latency
@@ -109,10 +114,13 @@ def parse():
                          "like-for-like partner of `full`)")
     ap.add_argument("--reps", type=int, default=5, help="repetitions of the K-step timed region inside one run (each with its own barriers and clock); "
                     "`value` is the MEDIAN repetition, min / max are reported next to it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-leg", action="store_true", help="skip the second timed loop (host -> host)")
-    ap.add_argument("--stage-times", action="store_true", help="print per-stage GPU times to stderr")
-    ap.add_argument("--no-also", action="store_true", help="default fp32 run only: skip the extra config-3 (forecast_n3, bf16) measurement attached under 'also'")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well: host -> host and one-in-flight latency legs, "
+                    "roofline, CPU baseline + parity vs the oracle, the full pipeline's stage timings, and (default workload) the other workloads "
+                    "under 'also'.  Off: set-up, warm-up, the timed repetitions and the outputs only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity vs the oracle")
+    ap.add_argument("--no-host-leg", action="store_true", help="with --full: skip the host -> host and one-in-flight latency legs")
+    ap.add_argument("--stage-times", action="store_true", help="with --full: print per-stage GPU times to stderr")
+    ap.add_argument("--no-also", action="store_true", help="with --full, default fp32 run only: skip the extra workloads attached under 'also'")
     ap.add_argument("--dump", default="", help="rank 0 saves the last step's gathered detections (npz: packed, counts) here (tests)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the timed path returned in its last step as "
                     "DIR/detections.npy (float32 [n,S,post,11], rows past a group's count zeroed) and DIR/counts.npy (float64 [n,S]), for "
@@ -120,7 +128,10 @@ def parse():
     pre, _ = ap.parse_known_args()
     if pre.config:  # a preset only moves the DEFAULTS: a flag given on the command line wins over it
         ap.set_defaults(**PRESETS[pre.config])
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.stage_times and not args.full:  # the stage events come from the roofline's instrumented steps
+        ap.error("--stage-times needs --full")
+    return args
 
 
 def kernel_sources_sha16():
@@ -656,7 +667,7 @@ def measure(args, env):
         # ---- second leg: the same K steps with every cloud starting in pinned host memory (H2D inside the clock, issued
         #      on the pass's own stream right in front of its voxelizer; the other stream's kernels overlap the copy)
         dt_host = None
-        if not args.no_host_leg:
+        if args.full and not args.no_host_leg:
             staging = {}
 
             def from_host(si, mb, st):
@@ -689,7 +700,7 @@ def measure(args, env):
         #      and the same with every cloud starting in pinned host memory -- with one cloud per pass that is the figure the reference's
         #      eval loop prints ("Total time per frame", tools/dist_test.py:204-217,240: a serial loop at samples_per_gpu = 1)
         dt_lat, dt_lat_h2h, n_lat = None, None, 0
-        if not args.no_host_leg:
+        if args.full and not args.no_host_leg:
             spare = streams[1:]
             del streams[1:]
             n_lat = max(1, min(args.steps, 30))
@@ -733,8 +744,9 @@ def measure(args, env):
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
         "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
         "dtype": "f32" if args.dtype == "fp32" else "bf16", "data": "synthetic",
+        "full": bool(args.full),  # False: the headline only; the legs, roofline, CPU baseline and extras below are null or absent
         "value_is": "clouds resident in HBM when the clock starts -> detections on the host (the bench contract's definition of `value`); "
-                    "SURVEY 8(d)'s points-on-host -> boxes-on-host figure is value_host_to_host (H2D inside the clock)",
+                    "SURVEY 8(d)'s points-on-host -> boxes-on-host figure is value_host_to_host (H2D inside the clock; --full)",
         "repetitions": {"n": len(rep_dt), "value_min": round(sweeps / max(rep_dt), 3), "value_median": round(sweeps / dt, 3), "value_max": round(sweeps / min(rep_dt), 3),
                         "ms_per_step_each": [round(1e3 * v / args.steps, 4) for v in rep_dt],
                         "what": "%d repetitions of the %d-step timed region in this run, each with its own barrier + synchronize + clock (max over ranks per "
@@ -767,7 +779,7 @@ def measure(args, env):
         out["config"]["pipeline"] = ("full: ten raw sweeps + transforms resident in HBM -> fd_sweep_assemble -> sweep -> fd_forecast_from_detections -> detections and "
                                      "trajectories on the host (one graph replay per pass)") if pipe == "full" else \
                                     "assembled: the plain pipeline on the clouds the full pipeline assembles (its like-for-like partner)"
-    if rank == 0 and pipe == "full":
+    if rank == 0 and args.full and pipe == "full":
         # the stages the full pipeline adds, each timed alone with HIP events (50 launches back to back after 5 warm-ups)
         from futuredet_amd import hip_ops
         from futuredet_amd.forecast import sweep_forecast
@@ -810,9 +822,9 @@ def measure(args, env):
                              "sweep in two of them) on a pass's packed detections, alone; latency-bound, <= 7 x 83 boxes per sweep",
             "trajectories_of_that_pass": int(fh["n_traj"].sum()), "trajectories_last_timed_pass": traj_last,
             "result_blob_bytes_per_pass": int(fo_.blob.numel())}
-    if rank == 0 and is_pp:
+    if rank == 0 and args.full and is_pp:
         out["roofline"] = None
-    elif rank == 0:
+    elif rank == 0 and args.full:
         # ---- roofline of the dominant kernel (sparse conv apply), from the events recorded in the timed region
         torch.cuda.synchronize()
         with torch.no_grad():
@@ -984,8 +996,8 @@ def main():
     cpus = dist_infer.pin_rank_cpus(local if not one_dev else rank, world)  # 256 logical CPUs / 8 ranks = 32 per rank
     env = dict(rank=rank, world=world, dev=dev, one_dev=one_dev, cpus=cpus)
     out = measure(args, env)
-    # The default run (BASELINE configs[1], fp32, one GPU) also measures, in this process and with the same program (set-up, warm-up,
-    # repetitions of the K-step timed region, host leg, one-in-flight latency legs, per-launch HIP events), the shapes the driver's one
+    # With --full, the default run (BASELINE configs[1], fp32, one GPU) also measures, in this process and with the same program (set-up,
+    # warm-up, repetitions of the K-step timed region, host leg, one-in-flight latency legs, per-launch HIP events), the shapes that one
     # command would otherwise never see, and attaches them under "also" (value / dtype / config stay the fp32 headline's):
     #   batch1          the headline workload with ONE cloud per pass, four passes in flight -- the shape of the round 1-4 series and of
     #                   the reference's eval loop (samples_per_gpu = 1); top-level value_batch1 / latency_ms_sweep are taken from it
@@ -1000,7 +1012,7 @@ def main():
     #                   full_pipeline assembles, its like-for-like partner)
     # Each extra reports its value and dtype only: the one JSON line has to stay short enough to be read back from the end of a run's output.
     is_default = (world == 1 and args.dtype == "fp32" and args.variant == "forecast_n0" and args.points == 300000 and args.batch == 2 and
-                  args.global_batch == 0 and args.scene == "dense" and args.class_name == "car" and not args.no_also)
+                  args.global_batch == 0 and args.scene == "dense" and args.class_name == "car" and args.full and not args.no_also)
     if is_default and out is not None:
         import copy
         import gc

@@ -2546,6 +2546,32 @@ def test_plain_bench_command_starts_its_own_ranks(hip):
         assert out.returncode != 0 and "device(s) are visible" in out.stderr and "n_gpus" not in out.stdout
 
 
+def test_bench_full_adds_the_legs_around_the_same_timed_region(hip, tmp_path):
+    """A plain bench run reports the headline only; --full adds the host -> host and latency legs and the roofline after the clock.
+    The timed region is the same program either way: both runs return the same detections for their last step, bit for bit."""
+    import json
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        dump = os.path.join(str(tmp_path), mode + ".npz")
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points", "20000",
+               "--no-cpu-baseline", "--dump", dump] + (["--full"] if mode == "full" else [])
+        out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines[mode] = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        dumps[mode] = np.load(dump)
+    p, f = lines["plain"], lines["full"]
+    for line in (p, f):
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3 and line["repetitions"]["n"] == 5
+    assert p["full"] is False and p["value_host_to_host"] is None and p["latency_ms_inflight1"] is None and "roofline" not in p
+    assert f["full"] is True and f["value_host_to_host"] > 0 and f["latency_ms_inflight1"] > 0 and f["roofline"]["launches_per_step"] > 0
+    for k in ("packed", "counts"):
+        assert np.array_equal(dumps["plain"][k], dumps["full"][k]), k
+
+
 @pytest.mark.parametrize("variant,precision", [("forecast_n0", "fp32"), ("forecast_n3", "bf16"), ("forecast_n3dtf", "fp32"), ("forecast_n3dtf", "bf16")])
 def test_decode_reads_the_head_output_in_place(hip, variant, precision):
     """predict_packed (the decode kernels read the conv plan's NHWC output through fd_map_view, velocities / labels / counts are

@@ -527,6 +527,22 @@ def test_bench_refuses_more_ranks_than_devices():
     assert out.returncode == 2 and "device(s) are visible" in out.stderr and "n_gpus" not in out.stdout
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain `bench.py` run measures the headline only; the other legs, the roofline, the CPU baseline and the other workloads need
+    --full.  --stage-times reads the roofline's instrumented steps, so it is refused without --full."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse()
+    assert not a.full and (a.steps, a.warmup, a.reps, a.dtype) == (20, 5, 5, "fp32")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--config", "3", "--stage-times"])
+    a = bench.parse()
+    assert a.full and a.stage_times and a.dtype == "bf16"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--stage-times"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_bench_cpu_baseline_reports_the_all_core_sample():
     """bench.cpu_baseline runs the oracle on every logical CPU of the host in-process (the sparse conv is one OpenMP region over output
     rows: no fork / join per tap) and matches the rows it is given against the oracle's detections."""

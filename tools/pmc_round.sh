@@ -4,10 +4,11 @@
 # passes (FETCH_SIZE / WRITE_SIZE / MFMA-busy) of a short serial run, and writes summaries to gpurun_out/<tag>_*.
 # PMC passes never combine with the hip/hsa/memory-copy trace domains.
 tag=$1; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-also"
+B="python $root/bench.py --full --no-also"  # --full: the profiled line carries the roofline and the CPU baseline
 rocprofv3 --kernel-trace --stats -d /tmp/kt_$tag -o kt --output-format csv -- $B "$@" > $out/${tag}_bench_profiled.json 2> /tmp/kt_$tag.err
 cp $(find /tmp/kt_$tag -name "*kernel_stats.csv" | head -1) $out/${tag}_kernel_stats.csv
 # one step in isolation: a serial run (--inflight 1).  Forward passes of the trace: 1 set-up + 2 StaticStep warm-up + 1 pre-capture run,

@@ -116,6 +116,6 @@ sha = bench.kernel_sources_sha16()
 if old.get("_meta", {}).get("csrc_sha16") not in (None, sha):
     old = {key: rec}  # records of other sources do not mix
 old["_meta"] = {"csrc_sha16": sha, "commit": None,
-                "how": "tools/pmc_round.sh: rocprofv3 --kernel-trace --pmc {FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES} -- python bench.py "
+                "how": "tools/pmc_round.sh: rocprofv3 --kernel-trace --pmc {FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES} -- python bench.py --full "
                        "<workload flags> --inflight 1 --graph 0 --steps 4 --warmup 2; FETCH_SIZE x2 (gfx950 wide-read correction); last two passes"}
 json.dump(old, open(path, "w"), indent=1)

@@ -65,7 +65,7 @@ for counter in ("FETCH_SIZE", "WRITE_SIZE", "SQ_VALU_MFMA_BUSY_CYCLES"):
         e = per.setdefault((d, k, r["Counter_Name"]), [0.0, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3])
         e[0] += float(r["Counter_Value"])
     with open(os.path.join(dst, "%s_pmc_%s_convs.txt" % (rnd, counter)), "w") as f:
-        f.write("# rocprofv3 --kernel-trace --pmc %s ... -- python bench.py --inflight 1 --graph 0 --steps 4 --warmup 2 --no-cpu-baseline "
+        f.write("# rocprofv3 --kernel-trace --pmc %s ... -- python bench.py --full --inflight 1 --graph 0 --steps 4 --warmup 2 --no-cpu-baseline "
                 "--no-host-leg; sparse / dense conv dispatches of the last two passes (counter summed over its XCC / SE rows)\n" % counter)
         f.write("dispatch kernel counter value duration_us\n")
         for (d, k, c), (v, us) in per.items():

@@ -13,7 +13,7 @@ python tools/window_stats.py 2>&1 | nf > $out/window_stats.txt
 tools/probes/gather_probe 16 > $out/gather_probe.txt 2>&1
 { FD_LIB_PATH=tools/probes/libfd_fd_decode_trace.so python tools/decode_trace.py 2>&1 | nf; } > $out/decode_trace.txt
 { FD_LIB_PATH=tools/probes/libfd_fd_spconv_c32_img.so python tools/skeleton_image_bench.py 1 2>&1 | nf; } > $out/skeleton_image_raw.txt
-for w in 0 -1; do FD_BF16_WIN=$w python bench.py --config 3 --no-cpu-baseline --steps 50 --reps 5 > $out/config3_win$w.json 2>/dev/null; done
+for w in 0 -1; do FD_BF16_WIN=$w python bench.py --full --config 3 --no-cpu-baseline --steps 50 --reps 5 > $out/config3_win$w.json 2>/dev/null; done
 python - <<PY > $out/config3_window_ab.txt
 import json
 for w in ("0", "-1"):
