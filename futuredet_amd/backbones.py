@@ -201,6 +201,9 @@ class SpMiddleResNetFHD(nn.Module):
 
     def forward(self, voxel_features, coors, batch_size, input_shape):
         if self.training:
+            if self.compute_dtype != torch.float32 and torch.is_grad_enabled():
+                raise NotImplementedError("SpMiddleResNetFHD: training runs the fp32 sparse convolution only; the %s path is inference-only "
+                                          "(set compute_dtype = torch.float32 to train)" % self.compute_dtype)
             return self.forward_generic(voxel_features, coors, batch_size, input_shape)
         coors = coors.int().contiguous()
         dev = voxel_features.device

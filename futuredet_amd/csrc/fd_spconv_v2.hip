@@ -693,6 +693,10 @@ int spconv_f32_compact_dispatch(const float *in, const void *wp, const float *bi
     FD_CASE(64, 64, 3, 128)
     FD_CASE(64, 128, 3, 128)
     FD_CASE(128, 128, 2, 128)
+    // the transposed shapes: input gradients of the strided 16 -> 32, 32 -> 64 and 64 -> 128 layers (fd_spconv_grad.hip)
+    FD_CASE(32, 16, 4, 128)
+    FD_CASE(64, 32, 4, 128)
+    FD_CASE(128, 64, 2, 128)
 #undef FD_CASE
 #undef FD_LAUNCH
     return 0;

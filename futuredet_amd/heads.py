@@ -12,10 +12,11 @@ each task a DCNSepHead -- two deformable FeatureAdaption modules, a cls_head for
 launch of fd_deform_adapt_nhwc) with every mode whose reference forward runs (not forecast_feature / wide_head, 64 shared channels);
 ``two_stage`` is False in every shipped config and raises.  In eval mode on the device the head runs on the convolution plan of dense_bf16.py
 (the only device path; a head it cannot take raises); predict() runs the HIP decode + rotated NMS (fd_centerpoint_decode) for
-all (sample, heat-map) groups in one call; the loss is training-only and out of scope of this path.
+all (sample, heat-map) groups in one call.  loss() (training, torch ops) covers the standard and dense heads.
 """
 import copy
 import logging
+from collections import defaultdict
 
 import torch
 from torch import nn
@@ -23,6 +24,35 @@ from torch import nn
 from . import hip_ops
 from .nn_utils import Sequential, deform_conv2d_v1, kaiming_init, weights_version
 from .registry import HEADS
+
+
+def _transpose_and_gather_feat(feat, ind):
+    """det3d/core/utils/center_utils.py:66-80: [B, C, H, W] maps at flat cells ind [B, M] -> [B, M, C]."""
+    feat = feat.permute(0, 2, 3, 1).contiguous()
+    feat = feat.view(feat.size(0), -1, feat.size(3))
+    return feat.gather(1, ind.unsqueeze(2).expand(ind.size(0), ind.size(1), feat.size(2)))
+
+
+def _focal_loss(out, target, ind, mask, cat):
+    """FastFocalLoss (det3d/models/losses/centernet_loss.py): CornerNet focal loss, positives gathered at ``ind``."""
+    mask = mask.float()
+    gt = torch.pow(1 - target, 4)
+    neg_loss = (torch.log(1 - out) * torch.pow(out, 2) * gt).sum()
+    pos_pred = _transpose_and_gather_feat(out, ind).gather(2, cat.unsqueeze(2))  # B x M x 1
+    num_pos = mask.sum()
+    pos_loss = (torch.log(pos_pred) * torch.pow(1 - pos_pred, 2) * mask.unsqueeze(2)).sum()
+    if num_pos == 0:
+        return -neg_loss
+    return -(pos_loss + neg_loss) / num_pos
+
+
+def _reg_loss(output, mask, ind, target):
+    """RegLoss (det3d/models/losses/centernet_loss.py): masked L1 per box dimension, normalised by the object count."""
+    pred = _transpose_and_gather_feat(output, ind)
+    mask = mask.float().unsqueeze(2)
+    loss = torch.nn.functional.l1_loss(pred * mask, target * mask, reduction="none")
+    loss = loss / (mask.sum() + 1e-4)
+    return loss.transpose(2, 0).sum(dim=2).sum(dim=1)
 
 
 class SepHead(nn.Module):
@@ -154,6 +184,14 @@ class CenterHead(nn.Module):
         self.class_names = [t["class_names"] for t in tasks]
         self.code_weights = code_weights
         self.box_n_dim = 9 if ("vel" in common_heads and "rot" in common_heads) else 7
+        # the loss weights of the forecast steps (center_head.py:278-288): only the velocity terms
+        fc_mask = None
+        if all(h in common_heads for h in ("vel", "rvel", "rot", "rrot")):
+            fc_mask = [0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 0, 0, 0, 0]
+        elif "vel" in common_heads and "rot" in common_heads:
+            fc_mask = [0, 0, 0, 0, 0, 0, 1, 1, 0, 0]
+        if fc_mask is not None and len(code_weights) == len(fc_mask):
+            self.code_weights_forecast = [float(c) * m for c, m in zip(code_weights, fc_mask)]
         self.weight = weight
         self.dataset = dataset
         self.in_channels = in_channels
@@ -228,8 +266,72 @@ class CenterHead(nn.Module):
             self._plan = (ver, HeadPlan(self, self.compute_dtype))  # raises ValueError for a head the kernels do not take
         return self._plan[1](x.to(self.compute_dtype).permute(0, 2, 3, 1).contiguous(), bev_map)
 
+    # ----------------------------------------------------------------------------------------------- loss
+    def _sigmoid(self, x):
+        return torch.clamp(x.sigmoid(), min=1e-4, max=1 - 1e-4)  # center_head.py:392-394 (out of place: the maps may be leaves)
+
     def loss(self, example, preds_dicts, **kwargs):
-        raise NotImplementedError("training losses (center_head.py:396-539) are outside the inference hot path")
+        """center_head.py:396-539 for the standard (n0 / n3 / pedestrian) and dense (n3dtf / n3dtfm) heads.  ``example`` carries the
+        reference pipeline's targets (hm / ind / mask / cat / anno_box, indexed [timestep][task]).  Returns the reference's dict of
+        per-task lists (loss, hm_loss, loc_loss, loc_loss_elem, num_positive); like the reference it replaces preds_dict["hm"] by the
+        clamped sigmoid and adds preds_dict["anno_box"]."""
+        for flag in ("reverse", "sparse", "classify", "wide_head"):
+            if getattr(self, flag):
+                raise NotImplementedError("CenterHead.loss: the %s head's loss is not implemented (standard and dense heads only)" % flag)
+        if self.dataset not in ("waymo", "nuscenes"):
+            raise NotImplementedError("CenterHead.loss: dataset %r (the reference handles waymo / nuscenes only)" % (self.dataset,))
+        T = self.timesteps
+        rets = []
+        for task_id, preds_dict in enumerate(preds_dicts):
+            preds_dict["hm"] = self._sigmoid(preds_dict["hm"])
+            if self.dense:
+                hm_loss = _focal_loss(preds_dict["hm"], example["hm"][task_id][0], example["ind"][task_id][0], example["mask"][task_id][0],
+                                      example["cat"][task_id][0])
+                target_box = example["anno_box"][task_id][0]
+            else:
+                hm_loss = _focal_loss(preds_dict["hm"], example["hm"][0][task_id], example["ind"][0][task_id], example["mask"][0][task_id],
+                                      example["cat"][0][task_id])
+                target_box = [example["anno_box"][i][task_id] for i in range(T)]
+            p = preds_dict
+            if "vel" in p and "rvel" in p and "rot" in p and "rrot" in p:
+                if self.dense:
+                    p["anno_box"] = torch.cat((p["reg"], p["height"], p["dim"], p["vel"], p["rvel"], p["rot"], p["rrot"]), dim=1)
+                else:
+                    p["anno_box"] = [torch.cat((p["reg"], p["height"], p["dim"], p["vel"][:, 2 * i:2 * i + 2], p["rvel"][:, 2 * i:2 * i + 2],
+                                                p["rot"], p["rrot"]), dim=1) for i in range(T)]
+            elif "vel" in p and "rot" in p:
+                if self.dense:
+                    p["anno_box"] = torch.cat((p["reg"], p["height"], p["dim"], p["vel"], p["rot"]), dim=1)
+                    target_box = target_box[..., [0, 1, 2, 3, 4, 5, 6, 7, -2, -1]]
+                else:
+                    p["anno_box"] = [torch.cat((p["reg"], p["height"], p["dim"], p["vel"][:, 2 * i:2 * i + 2], p["rot"]), dim=1) for i in range(T)]
+                    target_box = [target_box[i][..., [0, 1, 2, 3, 4, 5, 6, 7, -2, -1]] for i in range(T)]
+            else:
+                p["anno_box"] = [torch.cat((p["reg"], p["height"], p["dim"], p["rot"]), dim=1) for i in range(T)]
+                target_box = [target_box[i][..., [0, 1, 2, 3, 4, 5, -2, -1]] for i in range(T)]
+            loc_loss = []
+            if self.dense:
+                box_loss = _reg_loss(p["anno_box"], example["mask"][task_id][0], example["ind"][task_id][0], target_box)
+                loc_loss.append((box_loss * box_loss.new_tensor(self.code_weights)).sum())
+            else:
+                box_loss = [_reg_loss(p["anno_box"][i], example["mask"][0][task_id], example["ind"][0][task_id], target_box[i]) for i in range(T)]
+                for i in range(T):
+                    cw = self.code_weights if i == 0 else self.code_weights_forecast
+                    loc_loss.append((box_loss[i] * box_loss[i].new_tensor(cw)).sum())
+            loss = hm_loss + self.weight * sum(loc_loss)
+            if self.dense:
+                ret = {"loss": loss, "hm_loss": hm_loss.detach().cpu(), "loc_loss": loc_loss, "loc_loss_elem": box_loss.detach().cpu(),
+                       "num_positive": sum(sum(example["mask"][task_id][0].float()))}
+            else:
+                ret = {"loss": loss, "hm_loss": hm_loss.detach().cpu(), "loc_loss": loc_loss,
+                       "loc_loss_elem": [box_loss[i].detach().cpu() for i in range(T)],
+                       "num_positive": sum(sum(sum([example["mask"][i][task_id].float() for i in range(T)])))}
+            rets.append(ret)
+        merged = defaultdict(list)  # batch-key -> key-batch, as the reference returns it
+        for ret in rets:
+            for k, v in ret.items():
+                merged[k].append(v)
+        return merged
 
     # ----------------------------------------------------------------------------------------------- predict
     def _groups(self, preds_dicts):

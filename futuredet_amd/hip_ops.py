@@ -347,6 +347,60 @@ def pack_spconv_weight(w_kio, dtype=torch.float32):
     return host.to(dev)
 
 
+PACK_PLAIN, PACK_TRANSPOSED, PACK_FLIPPED_TRANSPOSED = 0, 1, 2  # fd_spconv_pack_weight_device modes: W[k], W[k]^T, W[K-1-k]^T
+
+
+def pack_spconv_weight_device(w_kio, mode=PACK_PLAIN):
+    """[K, Cin, Cout] float32 on the device -> fp32 fragment-ordered weights (fd_spconv_pack_weight byte for byte) of W[k], or, for
+    the input gradient, of W[k]^T / W[K-1-k]^T (a Cout -> Cin problem).  No host round trip."""
+    L = _lib.load()
+    w = _dev(w_kio.detach(), "w_kio", torch.float32)
+    K, cin, cout = w.shape
+    ci, co = (cout, cin) if mode else (cin, cout)
+    out = torch.empty((L.fd_spconv_packed_weight_bytes(K, ci, co, 0),), dtype=torch.uint8, device=w.device)
+    check(L.fd_spconv_pack_weight_device(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device")
+    return out
+
+
+def spconv_wgrad(feats, dy, nbr, n_out):
+    """dW[k] = sum_o feats[nbr[k][o]]^T dy[o] -> [K, Cin, Cout] float32 (deterministic, fd_spconv_wgrad)."""
+    L = _lib.load()
+    feats = _dev(feats, "feats", torch.float32)
+    dy = _dev(dy, "dy", torch.float32)
+    K, nstride = nbr.shape
+    cin, cout = feats.shape[1], dy.shape[1]
+    assert dy.shape[0] >= n_out
+    dw = torch.empty((K, cin, cout), dtype=torch.float32, device=feats.device)
+    ws = workspace.get("spconv_wgrad", L.fd_spconv_wgrad_workspace_bytes(K, n_out, cin, cout), feats.device)
+    check(L.fd_spconv_wgrad(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
+                            _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad")
+    return dw
+
+
+def rulebook_transpose(nbr, n_out, n_in):
+    """Input-stationary table inv[k][i] = o of an output-stationary rulebook ([K, stride64(n_in)] int32, -1 where no pair)."""
+    L = _lib.load()
+    K, nstride = nbr.shape
+    istride = max(64, (n_in + 63) // 64 * 64)
+    inv = torch.empty((K, istride), dtype=torch.int32, device=nbr.device)
+    check(L.fd_rulebook_transpose(_p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out, _p(getattr(nbr, "n_dev", None)), n_in, _p(inv),
+                                  istride, _stream()), "fd_rulebook_transpose")
+    return inv
+
+
+def dense_gather(grad, index, c):
+    """Backward of densify: [n, c] rows of ``grad`` ([B, c*D, H, W], any element strides) at the index's active cells."""
+    L = _lib.load()
+    if not (isinstance(grad, torch.Tensor) and grad.is_cuda and grad.dtype == torch.float32):
+        raise FutureDetHipError("dense_gather: grad must be a float32 tensor on the HIP device")
+    n = int(index.n)
+    feats = torch.empty((max(n, 1), c), dtype=torch.float32, device=grad.device)[:n]
+    sb, sc, sy, sx = grad.stride()
+    check(L.fd_dense_gather(_p(grad), sb, sc, sy, sx, index.D, _p(index.coords), n, _p(index.n_dev if index.static else None), c,
+                            _p(feats), _stream()), "fd_dense_gather")
+    return feats
+
+
 def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=False, out=None, balanced=None):
     L = _lib.load()
     feats = _dev(feats, "feats")

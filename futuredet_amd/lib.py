@@ -126,6 +126,12 @@ SIGNATURES = {
     "fd_deform_adapt_packed_weight_bytes": (c_size_t, [c_int]),
     "fd_deform_adapt_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "fd_deform_adapt_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fd_spconv_wgrad_workspace_bytes": (c_size_t, [c_int, c_i64, c_int, c_int]),
+    "fd_spconv_wgrad": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "fd_rulebook_transpose": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
+    "fd_spconv_pack_weight_device": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fd_dense_gather": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -53,8 +53,11 @@ class SparseConvTensor(object):
         row_of = idx.lookup(indices)
         self.index = idx
         self._true_channels = features.shape[1]
-        self.features = hip_ops.rows_permute(features.float().contiguous(), row_of, features.shape[1], torch.float32,
-                                             n_rows=idx.n)
+        src = features.float().contiguous()
+        if torch.is_grad_enabled() and src.requires_grad:
+            self.features = _RowsPermute.apply(src, row_of, idx.n)
+        else:
+            self.features = hip_ops.rows_permute(src, row_of, features.shape[1], torch.float32, n_rows=idx.n)
 
     @property
     def indices(self):
@@ -65,7 +68,10 @@ class SparseConvTensor(object):
 
     def dense(self, channels_first=True):
         feats = self.features.contiguous()
-        out = hip_ops.densify(feats, self.index)  # [B, C*D, H, W], channel = c*D + d
+        if torch.is_grad_enabled() and feats.requires_grad:
+            out = _Densify.apply(feats, self.index)
+        else:
+            out = hip_ops.densify(feats, self.index)  # [B, C*D, H, W], channel = c*D + d
         B, C, D = self.batch_size, feats.shape[1], self.index.D
         out = out.view(B, C, D, self.index.H, self.index.W)
         if not channels_first:
@@ -75,6 +81,75 @@ class SparseConvTensor(object):
 
 class SparseModule(nn.Module):
     pass
+
+
+# ------------------------------------------------------------------------------------------------ autograd (training)
+class _RowsPermute(torch.autograd.Function):
+    """features (input order) -> rows in index order; backward: the gather by ``row_of``."""
+
+    @staticmethod
+    def forward(ctx, src, row_of, n_rows):
+        ctx.save_for_backward(row_of)
+        return hip_ops.rows_permute(src, row_of, src.shape[1], torch.float32, n_rows=n_rows)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (row_of,) = ctx.saved_tensors
+        keep = row_of >= 0
+        g = grad[row_of.long().clamp(min=0)]
+        return g * keep[:, None].to(g.dtype), None, None
+
+
+class _Densify(torch.autograd.Function):
+    """SparseConvTensor.dense(): fd_densify forward, fd_dense_gather backward."""
+
+    @staticmethod
+    def forward(ctx, feats, index):
+        ctx.index = index
+        return hip_ops.densify(feats, index)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return hip_ops.dense_gather(grad.float(), ctx.index, grad.shape[1] // ctx.index.D), None
+
+
+class _SparseConvFunction(torch.autograd.Function):
+    """One fp32 sparse convolution on channel-padded tensors: feats [n_in, cin_p], weight [K, cin_p, cout_p], bias [cout_p] or None.
+
+    forward:  fd_spconv_apply with device-packed weights (no BN folding, no fused ReLU / residual);
+    backward: dX on fd_spconv_apply again (SubM: the same table with W[K-1-k]^T; strided: the transposed table with W[k]^T),
+              dW on fd_spconv_wgrad, dBias = sum of dY.  Saves the inputs only (an in-place ReLU follows the output)."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, bias, nbr, n_out, subm):
+        wpk = hip_ops.pack_spconv_weight_device(weight)
+        out = hip_ops.spconv_apply(feats, wpk, bias, nbr, n_out, weight.shape[2])
+        ctx.save_for_backward(feats, weight)
+        ctx.nbr, ctx.n_out, ctx.subm, ctx.has_bias = nbr, n_out, subm, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        feats, weight = ctx.saved_tensors
+        nbr, n_out = ctx.nbr, ctx.n_out
+        n_in, cin_p = feats.shape
+        dy = dy.float().contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            if ctx.subm:  # the SubM table is symmetric: nbr[k][o] = i <=> nbr[K-1-k][i] = o
+                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_FLIPPED_TRANSPOSED)
+                dx = hip_ops.spconv_apply(dy, wt, None, nbr, n_in, cin_p)
+            else:
+                inv = getattr(nbr, "inv", None)  # cached with the rulebook (indice_key)
+                if inv is None:
+                    inv = nbr.inv = hip_ops.rulebook_transpose(nbr, n_out, n_in)
+                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_TRANSPOSED)
+                dx = hip_ops.spconv_apply(dy, wt, None, inv, n_in, cin_p)
+        if ctx.needs_input_grad[1]:
+            dw = hip_ops.spconv_wgrad(feats, dy, nbr, n_out)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            db = dy[:n_out].sum(0)
+        return dx, dw, db, None, None, None
 
 
 class SparseConvolution(SparseModule):
@@ -160,10 +235,10 @@ class SparseConvolution(SparseModule):
 
     def forward(self, x):
         assert isinstance(x, SparseConvTensor)
-        if self.training and torch.is_grad_enabled() and self.weight.requires_grad:
-            raise NotImplementedError("the HIP sparse convolution is inference-only (no autograd): call under "
-                                      "torch.no_grad() / in eval mode; training is outside this path (SURVEY 2)")
         out_index, nbr = self.rulebook_for(x)
+        params = [self.weight] + ([self.bias] if self.bias is not None else [])
+        if torch.is_grad_enabled() and (x.features.requires_grad or (self.training and any(p.requires_grad for p in params))):
+            return self._forward_autograd(x, out_index, nbr)
         wpk, bias, cin_p, cout_p = self.packed_weight(torch.float32)
         feats = x.features
         if feats.shape[1] != cin_p:
@@ -171,6 +246,27 @@ class SparseConvolution(SparseModule):
         out = hip_ops.spconv_apply(feats.contiguous(), wpk, bias, nbr, out_index.n, cout_p)
         if cout_p != self.out_channels:
             out = out[:, : self.out_channels].contiguous()
+        y = SparseConvTensor(out, None, out_index.spatial_shape, x.batch_size, grid=x.grid, _index=out_index)
+        y.indice_dict = x.indice_dict
+        return y
+
+
+    def _forward_autograd(self, x, out_index, nbr):
+        """The differentiable path (fp32): padding and slicing are torch ops around _SparseConvFunction."""
+        if x.features.dtype != torch.float32:
+            raise NotImplementedError("sparse convolution training is fp32 only (features are %s)" % x.features.dtype)
+        K = int(np.prod(self.kernel_size))
+        cin_p, cout_p = pad_channels(self.in_channels), pad_channels(self.out_channels)
+        F = torch.nn.functional
+        w = F.pad(self.weight.float().reshape(K, self.in_channels, self.out_channels),
+                  (0, cout_p - self.out_channels, 0, cin_p - self.in_channels)).contiguous()
+        b = F.pad(self.bias.float(), (0, cout_p - self.out_channels)).contiguous() if self.bias is not None else None
+        feats = x.features
+        if feats.shape[1] != cin_p:
+            feats = F.pad(feats, (0, cin_p - feats.shape[1]))
+        out = _SparseConvFunction.apply(feats.contiguous(), w, b, nbr, out_index.n, self.subm)
+        if cout_p != self.out_channels:
+            out = out[:, : self.out_channels]
         y = SparseConvTensor(out, None, out_index.spatial_shape, x.batch_size, grid=x.grid, _index=out_index)
         y.indice_dict = x.indice_dict
         return y

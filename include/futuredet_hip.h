@@ -461,6 +461,32 @@ int fd_deform_adapt_pack_weight(const float *w_cls_oihw_host, const float *w_reg
 int fd_deform_adapt_nhwc(const void *x, int B, int H, int W, int C, int bf16, const float *off_w, const float *off_b, const float *offsets,
                          const void *wpacked, void *y, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: the backward pass of the fp32 sparse convolution (fd_spconv_grad.hip) -- spconv 1.0's indice_conv_backward /
+ * indice_subm_conv_backward (gradients of scn.py:99-141 under loss.backward()).  Purely additive: fd_abi_version() stays 8.
+ * fp32 only; cin, cout in {16, 32, 64, 128}.
+ *   fd_spconv_wgrad:  dw[k] = sum_o in[nbr[k][o]]^T . dy[o]  ([K, cin, cout] fp32, overwritten) for the output-stationary table of
+ *                     fd_rulebook; dy [n_out, cout].  Deterministic: per-(512-row chunk, tap) partials in `workspace`
+ *                     (fd_spconv_wgrad_workspace_bytes), summed in chunk order -- bit-identical whatever the launch.  n_out_dev as in
+ *                     fd_spconv_apply (rows >= the device count contribute nothing).  The input gradient is fd_spconv_apply itself:
+ *                     SubM: the same nbr with fd_spconv_pack_weight_device mode 2 (W[K-1-k]^T); strided: the table of
+ *                     fd_rulebook_transpose with mode 1 (W[k]^T), n_out = n_in.
+ *   fd_rulebook_transpose: inv[k][i] = o where nbr[k][o] = i, else -1 ([K, inv_stride], inv_stride >= n_in, every entry written).
+ *   fd_spconv_pack_weight_device: fd_spconv_pack_weight (dtype 0) on the device, byte for byte, of W'[k] = W[k] (mode 0),
+ *                     W[k]^T (mode 1: a [K, cout, cin] problem) or W[K-1-k]^T (mode 2); w_kio [K, cin, cout] fp32 device memory,
+ *                     wpacked fd_spconv_packed_weight_bytes(K, cin', cout', 0) bytes.
+ *   fd_dense_gather:  the backward of fd_densify: feats[row, ch] = dense[b * stride_b + (ch * D + z) * stride_c + y * stride_y + x *
+ *                     stride_x] for coords[row] = (b, z, y, x); rows >= min(n_rows, *n_dev) are written as 0.
+ * ------------------------------------------------------------------------------------------------- */
+size_t fd_spconv_wgrad_workspace_bytes(int K, int64_t n_out, int cin, int cout);
+int fd_spconv_wgrad(const float *in_feats, int64_t n_in, const float *dy, const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out,
+                    const int32_t *n_out_dev, int cin, int cout, float *dw, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_rulebook_transpose(const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out, const int32_t *n_out_dev, int64_t n_in, int32_t *inv,
+                          int64_t inv_stride, fd_stream_t stream);
+int fd_spconv_pack_weight_device(const float *w_kio, int K, int cin, int cout, int mode, void *wpacked, fd_stream_t stream);
+int fd_dense_gather(const float *dense, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x, int D, const int32_t *coords,
+                    int64_t n_rows, const int32_t *n_dev, int c, float *feats, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
