@@ -3,7 +3,8 @@
 The reference's config FILES load unchanged through Config.fromfile (tests check that against the parsed
 fixtures in tests/golden/configs.json); those files are not part of this repository, so benchmarks and GPU
 tests build the same dictionaries here.  Values: configs/centerpoint/nusc_centerpoint_forecast_n0_detection.py
-:6-15 (flags), :32-73 (model), :88-103 (test_cfg), :160-166 (voxel_generator).  ``dcn_head`` sets model.bbox_head.dcn_head (False in every shipped config)."""
+:6-15 (flags), :32-73 (model), :88-103 (test_cfg), :160-166 (voxel_generator), :75-86 (train_cfg.assigner: the standard sampler for n0 / n3, the trajectory sampler with
+radius_mult for n3dtf / n3dtfm).  ``dcn_head`` sets model.bbox_head.dcn_head (False in every shipped config)."""
 import itertools
 import logging
 
@@ -43,15 +44,18 @@ def centerpoint_config(variant="forecast_n0", class_name="car", voxel_size=(0.07
                     voxel_size=list(voxel_size[:2]), double_flip=False)
     voxel_generator = dict(range=list(pc_range), voxel_size=list(voxel_size), max_points_in_voxel=10,
                            max_voxel_num=list(max_voxel_num), double_flip=False)
+    trajectory = variant in ("forecast_n3dtf", "forecast_n3dtfm")
+    assigner = dict(target_assigner=dict(tasks=tasks), out_size_factor=osf, dense_reg=1, gaussian_overlap=0.1, max_objs=1000, min_radius=2,
+                    radius_mult=trajectory, sampler_type="trajectory" if trajectory else "standard")
     return ConfigDict(timesteps=timesteps, tasks=tasks, class_names=list(itertools.chain(*[t["class_names"] for t in tasks])),
-                      model=model, test_cfg=test_cfg, voxel_generator=voxel_generator, TWO_STAGE=False, DOUBLE_FLIP=False,
-                      DENSE=dense, BEV_MAP=bev, FORECAST_FEATS=ff)
+                      model=model, train_cfg=dict(assigner=assigner), test_cfg=test_cfg, voxel_generator=voxel_generator, TWO_STAGE=False,
+                      DOUBLE_FLIP=False, DENSE=dense, BEV_MAP=bev, FORECAST_FEATS=ff)
 
 
 def pointpillars_config(class_name="car", voxel_size=(0.2, 0.2, 8), pc_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0),
                         max_voxel_num=(30000, 60000)):
     """configs/centerpoint/nusc_centerpoint_pp_forecast_n3dtf_detection.py (:6-15 flags, :33-79 model, :95-107 test_cfg,
-    :165-170 voxel_generator) and its pedestrian twin: PointPillars reader/scatter + 3-stage RPN + the n3dtf head."""
+    :165-170 voxel_generator, train_cfg.assigner) and its pedestrian twin: PointPillars reader/scatter + 3-stage RPN + the n3dtf head."""
     timesteps, dense, ff, bev = 7, True, True, False
     tasks = [dict(num_class=1, class_names=[class_name])]
     model = dict(
@@ -73,6 +77,8 @@ def pointpillars_config(class_name="car", voxel_size=(0.2, 0.2, 8), pc_range=(-5
                     score_threshold=0.1, pc_range=list(pc_range[:2]), out_size_factor=osf, voxel_size=list(voxel_size[:2]))
     voxel_generator = dict(range=list(pc_range), voxel_size=list(voxel_size), max_points_in_voxel=20,
                            max_voxel_num=list(max_voxel_num))
+    assigner = dict(target_assigner=dict(tasks=tasks), out_size_factor=osf, gaussian_overlap=0.1, max_objs=1000, min_radius=2, radius_mult=True,
+                    sampler_type="trajectory")
     return ConfigDict(timesteps=timesteps, tasks=tasks, class_names=list(itertools.chain(*[t["class_names"] for t in tasks])),
-                      model=model, test_cfg=test_cfg, voxel_generator=voxel_generator, TWO_STAGE=False, DOUBLE_FLIP=False,
-                      DENSE=dense, BEV_MAP=bev, FORECAST_FEATS=ff)
+                      model=model, train_cfg=dict(assigner=assigner), test_cfg=test_cfg, voxel_generator=voxel_generator, TWO_STAGE=False,
+                      DOUBLE_FLIP=False, DENSE=dense, BEV_MAP=bev, FORECAST_FEATS=ff)

@@ -377,6 +377,29 @@ def spconv_wgrad(feats, dy, nbr, n_out):
     return dw
 
 
+def assign_targets(boxes, counts, classes, trajectory, cfg, out):
+    """AssignLabel's targets of a batch (fd_assign_targets): boxes [B, T, n_max, 12] fp32, counts [B, T] int32, classes / trajectory
+    [B, T, n_max] int32 (trajectory None: standard set only, cfg.n_sets must be 1); ``cfg`` a lib.TargetsCfg with T and n_max set;
+    ``out`` the flat buffers of TargetAssigner.outputs (hm, ind, mask, cat, anno_box, gt_boxes_and_cls, status), all overwritten."""
+    L = _lib.load()
+    boxes = _dev(boxes, "boxes", torch.float32)
+    B = boxes.shape[0]
+    assert tuple(boxes.shape) == (B, cfg.T, cfg.n_max, 12), (tuple(boxes.shape), cfg.T, cfg.n_max)
+    assert tuple(counts.shape) == (B, cfg.T) and tuple(classes.shape) == (B, cfg.T, cfg.n_max)
+    assert (trajectory is None) == (cfg.n_sets == 1)
+    if trajectory is not None:
+        assert tuple(trajectory.shape) == (B, cfg.T, cfg.n_max)
+        trajectory = _dev(trajectory, "trajectory", torch.int32)
+    U = cfg.n_tasks + (2 if cfg.n_sets == 3 else 0)
+    ws = workspace.get("targets", L.fd_targets_workspace_bytes(B, cfg.T, U, cfg.max_objs), boxes.device)
+    check(L.fd_assign_targets(_p(boxes), _p(_dev(counts, "counts", torch.int32)), _p(_dev(classes, "classes", torch.int32)), _p(trajectory), B,
+                              ctypes.byref(cfg), _p(_dev(out["hm"], "hm", torch.float32)), _p(_dev(out["ind"], "ind", torch.int64)),
+                              _p(_dev(out["mask"], "mask", torch.uint8)), _p(_dev(out["cat"], "cat", torch.int64)),
+                              _p(_dev(out["anno_box"], "anno_box", torch.float32)), _p(_dev(out["gt_boxes_and_cls"], "gt_boxes_and_cls", torch.float32)),
+                              _p(_dev(out["status"], "status", torch.int32)), _p(ws), ws.numel(), _stream()), "fd_assign_targets")
+    return out
+
+
 def rulebook_transpose(nbr, n_out, n_in):
     """Input-stationary table inv[k][i] = o of an output-stationary rulebook ([K, stride64(n_in)] int32, -1 where no pair)."""
     L = _lib.load()

@@ -44,6 +44,12 @@ class ForecastBuffers(ctypes.Structure):  # struct fd_forecast_buffers
                                         "status", "traj_kind", "traj_src", "traj_first", "traj_group", "n_traj")]
 
 
+class TargetsCfg(ctypes.Structure):  # struct fd_targets_cfg
+    _fields_ = [("H", c_int), ("W", c_int), ("T", c_int), ("n_max", c_int), ("max_objs", c_int), ("n_sets", c_int), ("n_tasks", c_int),
+                ("task_classes", c_int * 16), ("radius_mult", c_int), ("min_radius", c_int), ("out_size_factor", c_float), ("voxel_x", c_float),
+                ("voxel_y", c_float), ("pc_x", c_float), ("pc_y", c_float), ("gaussian_overlap", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -132,6 +138,9 @@ SIGNATURES = {
     "fd_rulebook_transpose": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "fd_spconv_pack_weight_device": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fd_dense_gather": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p]),
+    "fd_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fd_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(TargetsCfg), c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

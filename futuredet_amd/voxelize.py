@@ -88,8 +88,8 @@ class Voxelization(object):
 
 
 # names the shipped pipelines reference; they belong to dataset I/O / training and only need to resolve
-for _name in ("LoadPointCloudAnnotations", "Preprocess", "AssignLabel", "Reformat", "DoubleFlip",
-              "Empty"):
+for _name in ("LoadPointCloudAnnotations", "Preprocess", "Reformat", "DoubleFlip",
+              "Empty"):  # AssignLabel: futuredet_amd/targets.py
     def _make(name):
         def __init__(self, **kwargs):
             self.kwargs = kwargs

@@ -487,6 +487,43 @@ int fd_spconv_pack_weight_device(const float *w_kio, int K, int cin, int cout, i
 int fd_dense_gather(const float *dense, int64_t stride_b, int64_t stride_c, int64_t stride_y, int64_t stride_x, int D, const int32_t *coords,
                     int64_t n_rows, const int32_t *n_dev, int c, float *feats, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training targets: AssignLabel's heat maps and box rows (fd_targets.hip) -- det3d/datasets/pipelines/preprocess.py:336-910
+ * (NuScenesDataset branch) with gaussian_radius / draw_umich_gaussian of det3d/core/utils/center_utils.py:17-64, for a whole batch
+ * [B, T] and every target set in two launches.  Purely additive: fd_abi_version() stays 8.
+ * Inputs: boxes [B, T, n_max, 12] fp32 (x y z w l h vx vy rvx rvy rot rrot, as LoadPointCloudAnnotations leaves them: rot / rrot are
+ * passed through limit_period here), counts [B, T] int32 (objects per (sample, timestep); a count <= 0 is an empty timestep, a count
+ * above n_max reads n_max), classes [B, T, n_max] int32 (1-based class id over all tasks' class names, anything else: in no task),
+ * trajectory [B, T, n_max] int32 (0 static, 1 linear, 2 nonlinear, anything else: not in the trajectory set; read only when
+ * n_sets = 3).
+ * Sets (n_sets = 1: standard; 3: + trajectory (one task of 3 classes, preprocess.py:571-733) + forecast (one task of 7 classes: every
+ * timestep's objects in timestep order, class = timestep + 1, preprocess.py:737-897; needs T <= 7)).  Maps per timestep
+ * U = n_tasks (+ 2); map u has C_u channels (task_classes[u], then 3, then 7); Csum = their sum.
+ * Outputs, every element written by the call:
+ *   hm               fp32, one array of T * Csum * B * H * W elements (16-byte aligned, room for that count rounded up to 4):
+ *                    [T][map u: [B][C_u][H][W]], map (t, u) starting at element (t * Csum + sum_{u' < u} C_u') * B * H * W;
+ *   ind / cat        int64 [T][U][B][max_objs], mask uint8 and anno_box fp32 [.., 14] of the same shape (preprocess.py:519-531);
+ *   gt_boxes_and_cls fp32 [n_sets][T][B][max_objs][13] (preprocess.py:548-567);
+ *   status           int32 [B][T][n_sets]: 0, or 1 = the set holds more than max_objs objects (the reference's assert, :562).
+ * workspace >= fd_targets_workspace_bytes(B, T, U, max_objs).  gaussian_overlap is the config's python float: the constants of
+ * gaussian_radius are derived from it as numpy derives them. */
+#define FD_TARGETS_MAX_TASKS 16
+typedef struct fd_targets_cfg {
+    int H, W;        /* heat-map rows and columns: grid[1] // out_size_factor, grid[0] // out_size_factor */
+    int T, n_max, max_objs;
+    int n_sets;      /* 1 or 3 */
+    int n_tasks;     /* tasks of the standard set */
+    int task_classes[FD_TARGETS_MAX_TASKS];
+    int radius_mult; /* 0 / 1 */
+    int min_radius;
+    float out_size_factor, voxel_x, voxel_y, pc_x, pc_y;
+    double gaussian_overlap;
+} fd_targets_cfg;
+size_t fd_targets_workspace_bytes(int B, int T, int maps_per_step, int max_objs);
+int fd_assign_targets(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory, int B,
+                      const fd_targets_cfg *cfg, float *hm, int64_t *ind, uint8_t *mask, int64_t *cat, float *anno_box,
+                      float *gt_boxes_and_cls, int32_t *status, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
