@@ -233,5 +233,23 @@ class PointPillarsScatter(nn.Module):
     def forward(self, voxel_features, coords, batch_size, input_shape, n_dev=None):
         self.nx = int(input_shape[0])
         self.ny = int(input_shape[1])
-        return hip_ops.pillar_scatter(voxel_features, coords.int().contiguous(), n_dev, batch_size, self.ny, self.nx,
+        coords = coords.int().contiguous()
+        if n_dev is None and torch.is_grad_enabled() and voxel_features.requires_grad:
+            return _ScatterFn.apply(voxel_features, coords, batch_size, self.ny, self.nx, self.dense_channels_last)
+        return hip_ops.pillar_scatter(voxel_features, coords, n_dev, batch_size, self.ny, self.nx,
                                       channels_last=self.dense_channels_last)
+
+
+class _ScatterFn(torch.autograd.Function):
+    """PointPillarsScatter with its backward: d(pillar row) = dcanvas[b, :, y, x] (fd_dense_gather with D = 1, any canvas strides)."""
+
+    @staticmethod
+    def forward(ctx, feats, coords, batch_size, ny, nx, channels_last):
+        ctx.coords = coords
+        return hip_ops.pillar_scatter(feats, coords, None, batch_size, ny, nx, channels_last=channels_last)
+
+    @staticmethod
+    def backward(ctx, dcanvas):
+        d = hip_ops.pillar_scatter_backward(dcanvas.float(), ctx.coords)
+        ctx.coords = None
+        return d, None, None, None, None, None

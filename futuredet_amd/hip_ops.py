@@ -859,6 +859,72 @@ def pillar_encode(voxels, num_points, coors4, n_dev, geom, layers, with_distance
     return out
 
 
+def pillar_train_workspace_bytes(m, max_points):
+    return int(_lib.load().fd_pillar_train_workspace_bytes(int(m), int(max_points)))
+
+
+def _pillar_train_args(voxels, num_points, coors4, geom, w1, g1, b1, w2, g2, b2, with_distance):
+    voxels = _dev(voxels, "voxels", torch.float32)
+    M, P, ndim = voxels.shape
+    for t, name in ((w1, "w1"), (g1, "gamma1"), (b1, "beta1"), (w2, "w2"), (g2, "gamma2"), (b2, "beta2")):
+        _dev(t, name, torch.float32)
+    return [_p(voxels), _p(_dev(num_points, "num_points", torch.int32)), _p(_dev(coors4, "coors4", torch.int32)), M, P, ndim,
+            int(bool(with_distance)), float(geom[0]), float(geom[1]), float(geom[2]), float(geom[3])]
+
+
+def pillar_train_forward(voxels, num_points, coors4, geom, w1, g1, b1, eps1, w2, g2, b2, eps2, with_distance=False, out=None,
+                         workspace=None):
+    """fd_pillar_train_forward: PillarFeatureNet (two PFN layers, 32 -> 64) on batch statistics.  voxels [M,P,ndim] f32,
+    num_points [M] / coors4 [M,4] int32, geom = (vx, vy, x_offset, y_offset), w1 [32, Fin], w2 [64, 64], gamma / beta per layer.
+    Returns (out [M, 64], mean1, var1 [32], mean2, var2 [64], workspace); the variances are biased, the workspace (uint8) holds
+    what pillar_train_backward needs."""
+    L = _lib.load()
+    args = _pillar_train_args(voxels, num_points, coors4, geom, w1, g1, b1, w2, g2, b2, with_distance)
+    M, P = args[3], args[4]
+    dev = voxels.device
+    nbytes = L.fd_pillar_train_workspace_bytes(M, P)
+    if workspace is None:
+        workspace = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((M, w2.shape[0]), dtype=torch.float32, device=dev)
+    stats = torch.empty((2 * w1.shape[0] + 2 * w2.shape[0],), dtype=torch.float32, device=dev)
+    u1, u2 = w1.shape[0], w2.shape[0]
+    mean1, var1, mean2, var2 = stats[:u1], stats[u1:2 * u1], stats[2 * u1:2 * u1 + u2], stats[2 * u1 + u2:]
+    check(L.fd_pillar_train_forward(*args, _p(w1), _p(g1), _p(b1), u1, float(eps1), _p(w2), _p(g2), _p(b2), u2, float(eps2),
+                                    _p(_dev(out, "out", torch.float32)), _p(mean1), _p(var1), _p(mean2), _p(var2), _p(workspace),
+                                    workspace.numel(), _stream()), "fd_pillar_train_forward")
+    return out, mean1, var1, mean2, var2, workspace
+
+
+def pillar_train_backward(dout, voxels, num_points, coors4, geom, w1, g1, b1, w2, g2, b2, workspace, with_distance=False):
+    """fd_pillar_train_backward: dout [M, 64] -> (dw1, dgamma1, dbeta1, dw2, dgamma2, dbeta2); ``workspace`` as the matching
+    pillar_train_forward left it."""
+    L = _lib.load()
+    args = _pillar_train_args(voxels, num_points, coors4, geom, w1, g1, b1, w2, g2, b2, with_distance)
+    dout = _dev(dout, "dout", torch.float32)
+    assert tuple(dout.shape) == (args[3], w2.shape[0]), (tuple(dout.shape), args[3])
+    dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+    dg1, db1, dg2, db2 = torch.empty_like(g1), torch.empty_like(b1), torch.empty_like(g2), torch.empty_like(b2)
+    check(L.fd_pillar_train_backward(*args, _p(w1), _p(g1), _p(b1), w1.shape[0], _p(w2), _p(g2), _p(b2), w2.shape[0], _p(dout),
+                                     _p(dw1), _p(dg1), _p(db1), _p(dw2), _p(dg2), _p(db2), _p(workspace), workspace.numel(), _stream()),
+          "fd_pillar_train_backward")
+    return dw1, dg1, db1, dw2, dg2, db2
+
+
+def pillar_scatter_backward(dcanvas, coors4):
+    """Backward of PointPillarsScatter: d(pillar row m) = dcanvas[b, :, y, x] for coors4[m] = (b, 0, y, x) -- fd_dense_gather with D = 1
+    on any canvas strides (NCHW or channels-last).  Returns [M, C] float32."""
+    L = _lib.load()
+    if not (isinstance(dcanvas, torch.Tensor) and dcanvas.is_cuda and dcanvas.dtype == torch.float32):
+        raise FutureDetHipError("pillar_scatter_backward: dcanvas must be a float32 tensor on the HIP device")
+    coors4 = _dev(coors4, "coors4", torch.int32)
+    n, c = coors4.shape[0], dcanvas.shape[1]
+    feats = torch.empty((max(n, 1), c), dtype=torch.float32, device=dcanvas.device)[:n]
+    sb, sc, sy, sx = dcanvas.stride()
+    check(L.fd_dense_gather(_p(dcanvas), sb, sc, sy, sx, 1, _p(coors4), n, None, c, _p(feats), _stream()), "fd_dense_gather")
+    return feats
+
+
 def pillar_scatter(feats, coors4, n_dev, batch_size, ny, nx, out_dtype=None, channels_last=False, out=None, zero_first=True):
     """fd_pillar_scatter -> [B, C, ny, nx] canvas (NCHW, or channels-last memory when asked)."""
     L = _lib.load()

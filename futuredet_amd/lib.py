@@ -138,6 +138,13 @@ SIGNATURES = {
     "fd_rulebook_transpose": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "fd_spconv_pack_weight_device": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fd_dense_gather": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p]),
+    "fd_pillar_train_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "fd_pillar_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                        c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_pillar_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fd_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "fd_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(TargetsCfg), c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

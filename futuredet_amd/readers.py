@@ -1,4 +1,5 @@
-"""Readers (det3d/models/readers).  VoxelFeatureExtractorV3: per-voxel mean of the point slots."""
+"""Readers (det3d/models/readers).  VoxelFeatureExtractorV3: per-voxel mean of the point slots.  PillarFeatureNet: the PointPillars
+reader on fd_pillar_encode (eval) and fd_pillar_train_forward / _backward (train)."""
 import torch
 from torch import nn
 
@@ -29,7 +30,7 @@ class VoxelFeatureExtractorV3(nn.Module):
 class PFNLayer(nn.Module):
     """Parameter holder with the state_dict keys of det3d/models/readers/pillar_encoder.py:15-55 (linear.weight,
     norm.*).  The layer itself (Linear, BatchNorm, ReLU, max over the pillar's points, concat) is evaluated inside
-    fd_pillar_encode; there is no per-layer torch forward."""
+    fd_pillar_encode (eval) or fd_pillar_train_forward / _backward (train); there is no per-layer torch forward."""
 
     def __init__(self, in_channels, out_channels, norm_cfg=None, last_layer=False):
         super().__init__()
@@ -48,7 +49,10 @@ class PFNLayer(nn.Module):
 @READERS.register_module
 class PillarFeatureNet(nn.Module):
     """det3d/models/readers/pillar_encoder.py:58-164.  In eval mode on the GPU the whole reader is one HIP launch
-    (fd_pillar_encode); the torch modules only define the parameters / state_dict.  Training is outside this path."""
+    (fd_pillar_encode) with BatchNorm folded from the running statistics.  In training mode (the shipped stack, two PFN layers
+    32 -> 64, fp32) it runs on fd_pillar_train_forward / fd_pillar_train_backward: BatchNorm on batch statistics over every
+    point slot of the batch, gradients for both layers' Linear and BatchNorm parameters, and the running statistics updated
+    in place with the BatchNorm modules' own momentum.  The torch modules only define the parameters / state_dict."""
 
     def __init__(self, num_input_features=4, num_filters=(64,), with_distance=False, voxel_size=(0.2, 0.2, 4),
                  pc_range=(0, -40, -3, 70.4, 40, 1), norm_cfg=None):
@@ -87,11 +91,74 @@ class PillarFeatureNet(nn.Module):
 
     def forward(self, features, num_voxels, coors, n_dev=None):
         if self.training:
-            raise NotImplementedError("PillarFeatureNet runs as one fused inference kernel (fd_pillar_encode); training is outside "
-                                      "the hot path (SURVEY 2)")
+            return self._forward_train(features, num_voxels, coors)
         return hip_ops.pillar_encode(features, num_voxels.int(), coors.int().contiguous(), n_dev,
                                      (self.vx, self.vy, self.x_offset, self.y_offset), self._layers(features.device),
                                      with_distance=self._with_distance, out_dtype=self.compute_dtype)
+
+
+    def _forward_train(self, features, num_voxels, coors):
+        if self.compute_dtype != torch.float32:
+            raise NotImplementedError("PillarFeatureNet: training runs in fp32 only; the %s reader is inference-only (set compute_dtype = "
+                                      "torch.float32 to train)" % self.compute_dtype)
+        units = [pfn.units for pfn in self.pfn_layers]
+        if units != [32, 64]:
+            raise NotImplementedError("PillarFeatureNet: training supports the shipped PFN stack num_filters=[64, 64] (units 32 -> 64, "
+                                      "fd_pillar_train_forward), not units %s" % units)
+        l1, l2 = self.pfn_layers
+        n1, n2 = l1.norm, l2.norm
+        geom = (self.vx, self.vy, self.x_offset, self.y_offset)
+        spec = (geom, n1.eps, n2.eps, self._with_distance)
+        voxels = features.float().contiguous()
+        out, stats = _PillarTrain.apply(voxels, num_voxels.int().contiguous(), coors.int().contiguous(), l1.linear.weight.contiguous(),
+                                        n1.weight.contiguous(), n1.bias.contiguous(), l2.linear.weight.contiguous(), n2.weight.contiguous(),
+                                        n2.bias.contiguous(), spec)
+        n = voxels.shape[0] * voxels.shape[1]
+        with torch.no_grad():
+            u1 = n1.num_features
+            for bn, mean, var in ((n1, stats[:u1], stats[u1:2 * u1]), (n2, stats[2 * u1:2 * u1 + n2.num_features], stats[2 * u1 + n2.num_features:])):
+                _update_running_stats(bn, mean, var, n)
+        return out
+
+
+def _update_running_stats(bn, mean, var, n):
+    """torch's BatchNorm rule, as in-place ops on the module's buffers (so weights_version sees them): num_batches_tracked += 1,
+    running_mean <- (1 - f) running_mean + f mean, running_var <- (1 - f) running_var + f var * n / (n - 1), f = momentum, or
+    1 / num_batches_tracked (cumulative average) when momentum is None."""
+    if not bn.track_running_stats or bn.running_mean is None:
+        return
+    bn.num_batches_tracked.add_(1)
+    f = (1.0 / float(bn.num_batches_tracked)) if bn.momentum is None else bn.momentum
+    bn.running_mean.mul_(1.0 - f).add_(mean, alpha=f)
+    bn.running_var.mul_(1.0 - f).add_(var, alpha=f * n / (n - 1))
+
+
+class _PillarTrain(torch.autograd.Function):
+    """The train-mode reader over fd_pillar_train_forward / _backward.  Returns (out [M, 64], stats [192] = mean1, var1, mean2,
+    var2 with biased variances); the stats carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, voxels, num_points, coors4, w1, g1, b1, w2, g2, b2, spec):
+        geom, eps1, eps2, wd = spec
+        out, mean1, var1, mean2, var2, ws = hip_ops.pillar_train_forward(voxels, num_points, coors4, geom, w1, g1, b1, eps1, w2, g2, b2,
+                                                                         eps2, with_distance=wd)
+        stats = torch.cat([mean1, var1, mean2, var2])
+        ctx.inputs = (voxels, num_points, coors4, w1, g1, b1, w2, g2, b2)
+        ctx.ws = ws
+        ctx.spec = spec
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, dstats):
+        voxels, num_points, coors4, w1, g1, b1, w2, g2, b2 = ctx.inputs
+        geom, _, _, wd = ctx.spec
+        if dout is None:
+            dout = torch.zeros((voxels.shape[0], w2.shape[0]), dtype=torch.float32, device=voxels.device)
+        grads = hip_ops.pillar_train_backward(dout.float().contiguous(), voxels, num_points, coors4, geom, w1, g1, b1, w2, g2, b2, ctx.ws,
+                                              with_distance=wd)
+        ctx.inputs = ctx.ws = None
+        return (None, None, None) + tuple(grads) + (None,)
 
 
 def _drop_packed(module, incompatible_keys=None):

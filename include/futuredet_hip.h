@@ -524,6 +524,33 @@ int fd_assign_targets(const float *boxes, const int32_t *counts, const int32_t *
                       const fd_targets_cfg *cfg, float *hm, int64_t *ind, uint8_t *mask, int64_t *cat, float *anno_box,
                       float *gt_boxes_and_cls, int32_t *status, void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: PillarFeatureNet in train mode (fd_pillars_grad.hip) -- det3d/models/readers/pillar_encoder.py:15-164 with
+ * BatchNorm1d on batch statistics, and its backward.  Purely additive: fd_abi_version() stays 8.  fp32; the shipped stack only:
+ * two PFN layers, units1 = 32 (+32 repeated max) -> units2 = 64; max_points (P) in [1, 32]; N = m * max_points > 1 rows, every
+ * point slot of every pillar (padded slots included, as torch's BatchNorm1d counts them).
+ *   inputs as fd_pillar_encode (voxels [m, P, ndim], num_points [m], coors4 [m, 4], geometry); w1 [32, ndim+5(+1)],
+ *   w2 [64, 64] (the linear weights), gamma / beta the BatchNorm weight / bias, eps1 / eps2 their eps.
+ *   fd_pillar_train_forward: out [m, 64] fp32 (the reader's output), mean1 / var1 [32] and mean2 / var2 [64]: each layer's batch
+ *                     mean and BIASED variance (the caller updates the running statistics).  Leaves in `workspace` what the
+ *                     backward needs (per-pillar arg-max bytes, statistics): keep it untouched until the backward has run.
+ *   fd_pillar_train_backward: dout [m, 64] -> dw1 [32, ndim+5(+1)], dgamma1 / dbeta1 [32], dw2 [64, 64], dgamma2 / dbeta2 [64],
+ *                     all overwritten; same inputs and workspace as the forward call it follows.
+ * workspace >= fd_pillar_train_workspace_bytes(m, max_points) (0 = invalid sizes).  No allocation, no synchronisation: both calls
+ * can be captured into a graph.  Deterministic: fixed-order block partials and a fixed-order double-precision combine, no atomics.
+ * ------------------------------------------------------------------------------------------------- */
+size_t fd_pillar_train_workspace_bytes(int64_t m, int max_points);
+int fd_pillar_train_forward(const float *voxels, const int32_t *num_points, const int32_t *coors4, int64_t m, int max_points, int ndim,
+                            int with_distance, float vx, float vy, float x_offset, float y_offset, const float *w1, const float *gamma1,
+                            const float *beta1, int units1, float eps1, const float *w2, const float *gamma2, const float *beta2, int units2,
+                            float eps2, float *out, float *mean1, float *var1, float *mean2, float *var2, void *workspace,
+                            size_t workspace_bytes, fd_stream_t stream);
+int fd_pillar_train_backward(const float *voxels, const int32_t *num_points, const int32_t *coors4, int64_t m, int max_points, int ndim,
+                             int with_distance, float vx, float vy, float x_offset, float y_offset, const float *w1, const float *gamma1,
+                             const float *beta1, int units1, const float *w2, const float *gamma2, const float *beta2, int units2,
+                             const float *dout, float *dw1, float *dgamma1, float *dbeta1, float *dw2, float *dgamma2, float *dbeta2,
+                             void *workspace, size_t workspace_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
