@@ -28,14 +28,20 @@
 //     (double buffered one tap ahead when it is small).  A wave never shares an accumulator element with another
 //     wave: no atomics, no barriers in the main loop, fixed summation order (taps ascending) -> deterministic.
 //   * epilogue: bias (+ residual) (+ ReLU) on the LDS tile, written out with 16-byte row-contiguous stores.
-#include "fd_common.h"
+//
+// What happens per chunk around the item loop -- LDS layout, list-entry encoding, accumulator swizzle, range / chunk resolution,
+// slice prefetch and staging, tile init, compaction, work list, epilogue -- is shared with the 32-pair kernel (fd_spconv_c32.hip)
+// and lives in fd_spconv_chunk.h.  This file owns the 16-pair unit of work (wave -> column slice / tap split / row set mapping,
+// gather, weight slice in registers and its in-place reload, the 16x16x4 MFMA loop with its scheduling barriers), its dispatch
+// table, the phase trace (FD_V2_TRACE) and the work-balanced ranges.
+#include "fd_spconv_chunk.h"
 
 namespace {
 
+namespace sk = fd::skeleton;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int kMaxTaps = 27;
 
 // Phase timeline for tuning builds only (tools/probes/build_trace.sh compiles this file with -DFD_V2_TRACE into a
 // separate library; the product library contains none of it): thread 0 of every workgroup stamps s_memtime at the
@@ -56,6 +62,12 @@ __device__ unsigned long long *g_trace;
 #endif
 
 
+// tap splits of a COUT-column tile (the kernel's TS; the host sizes the LDS request with it).  32 / 64 columns: instead of two row
+// halves (whose separately compacted lists pad 17 % more MFMA rows) the two waves of a column slice split the TAPS (even / odd)
+// over the full tile and accumulate into private copies of the tile that the epilogue adds up; the LDS for the second copy is
+// there anyway (these layers run two workgroups per CU).  16 columns keep four row quarters: measured faster.
+constexpr int tap_splits(int cout) { return (cout == 32 || cout == 64) ? 2 : 1; }
+
 template <int CIN, int COUT, int TM, int DEPTH>
 __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restrict__ in, const float4 *__restrict__ wp,
                                                           const float *__restrict__ bias, const float *__restrict__ residual, int relu,
@@ -65,177 +77,48 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     constexpr int NB = COUT / 16, NC = CIN / 16;
     constexpr int WC = NB == 8 ? 4 : (NB >= 2 ? 2 : 1);  // column splits across the 4 waves (64 columns: 2 x 32)
     constexpr int NBW = NB / WC;          // 16-column blocks per wave
-    // 32 / 64 columns: instead of two row halves (whose separately compacted lists pad 17 % more MFMA rows) the two waves of a
-    // column slice split the TAPS (even / odd) over the full tile and accumulate into private copies of the tile that
-    // the epilogue adds up; the LDS for the second copy is there anyway (these layers run two workgroups per CU).
-    constexpr int TS = (NB == 2 || NB == 4) ? 2 : 1;  // tap splits (16 columns keep four row quarters: measured faster)
+    constexpr int TS = tap_splits(COUT);
     constexpr int WR = 4 / (WC * TS);             // row splits
-    constexpr int RW = TM / WR;                   // rows in a wave's row set
     constexpr int NACC = NBW;  // one accumulator chain per column block (dependent 16x16x4 MFMAs issue back to back at full rate)
-    static_assert((TM == 128 || TM == 64) && RW >= 16, "local row uses 8 bits (0..TM, TM = scratch row)");
-    constexpr int kMaxItems = kMaxTaps * (TM / 16);           // per wave: taps x 16-row groups
-    constexpr int kPad = (int)(0xffffff00u | (unsigned)TM);  // list padding: input offset out of range, local row = TM (scratch row)
+    static_assert((TM == 128 || TM == 64) && TM / WR >= 16, "local row uses 8 bits (0..TM, TM = scratch row)");
+    constexpr int kPad = sk::pad_entry(TM);
+    constexpr sk::Layout L = sk::layout(TM, COUT, TS, 16);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int *s_list = reinterpret_cast<int *>(smem);                                            // [K][TM] raw nbr, then compacted entries
-    unsigned short *s_items = reinterpret_cast<unsigned short *>(s_list + kMaxTaps * TM);   // [4 waves][kMaxItems]
-    unsigned char *s_cnt = reinterpret_cast<unsigned char *>(s_items + 4 * kMaxItems);      // [K][4] (<= 128 each)
-    int *s_pad = reinterpret_cast<int *>(s_cnt + 112);                                      // 16 padding entries (tail of the work list)
-    float *s_acc = reinterpret_cast<float *>(s_pad + 16);                                   // [TM + 1][COUT], 16-byte aligned for TM = 64 and 128
+    int *s_list = reinterpret_cast<int *>(smem + L.list);
+    unsigned short *s_items = reinterpret_cast<unsigned short *>(smem + L.items);
+    unsigned char *s_cnt = smem + L.cnt;
+    int *s_pad = reinterpret_cast<int *>(smem + L.pad);
+    float *s_acc = reinterpret_cast<float *>(smem + L.acc);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: what derives from it stays in SGPRs
-    // ---- this workgroup's row range, cut into equal chunks of at most TM rows (multiples of 16)
-    int r_begin, r_end;
-    if (n_out_dev) n_out = fd::device_count(n_out, n_out_dev);  // capacity launch (see fd_common.h)
-    if (ranges) {
-        r_begin = ranges[blockIdx.x];
-        r_end = ranges[blockIdx.x + 1];
-    } else {
-        if (n_out_dev)  // the equal-rows split is made here, from the device's count
-            rows_per_range = (((n_out + (int)gridDim.x - 1) / (int)gridDim.x) + 15) & ~15;
-        const int64_t b = (int64_t)blockIdx.x * rows_per_range;
-        r_begin = (int)(b < n_out ? b : n_out);
-        r_end = (int)(b + rows_per_range < n_out ? b + rows_per_range : n_out);
-    }
-    if (r_end > n_out) r_end = n_out;
+    int r_begin, r_end, n_chunks, chunk_rows;
+    sk::resolve_range(n_out, n_out_dev, ranges, rows_per_range, r_begin, r_end);
     if (r_begin >= r_end) return;
     FD_T(0);
-    const int n_chunks = (r_end - r_begin + TM - 1) / TM;
-    const int chunk_rows = (((r_end - r_begin + n_chunks - 1) / n_chunks) + 15) & ~15;
-    // rulebook slice of a chunk, one register per 256 entries; loads are branch-free (clamped address, select on use)
-    constexpr int NPRE = (kMaxTaps * TM + 255) / 256;
-    int pre[NPRE];
-    auto fetch_slice = [&](int row0) {
-#pragma unroll
-        for (int i = 0; i < NPRE; ++i) {
-            const int t = tid + i * 256;
-            int k = t / TM;
-            const int r = t - k * TM;
-            k = k < K ? k : K - 1;
-            int64_t o = (int64_t)row0 + r;
-            o = o < nbr_stride ? o : nbr_stride - 1;
-            pre[i] = nbr[(int64_t)k * nbr_stride + o];
-        }
-    };
-    fetch_slice(r_begin);
+    sk::cut_chunks<TM>(r_begin, r_end, n_chunks, chunk_rows);
+    int pre[sk::kSliceRegs<TM>];
+    sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, r_begin);
 
     const int lrow = lane & 15, lq = lane >> 4;
     const int wc = wave % WC, wr = TS == 1 ? wave / WC : 0, ts = TS == 1 ? 0 : wave / WC;
     const int cb = wc * NBW * 16;
-    constexpr int kRowShift = COUT == 16 ? 6 : COUT == 32 ? 7 : COUT == 64 ? 8 : 9;  // log2(COUT * 4)
-    static_assert((COUT * 4) == (1 << kRowShift), "COUT must be 16, 32, 64 or 128");
-    // 16-byte slot swizzle of the accumulator tile: slot ^= f(row) so that 16 different rows at one column slot spread
-    // over the 16 slots of a 256-byte bank row (COUT 64/128: row & 15; 32: two rows per bank row; 16: four)
-    constexpr int kSwzShift = COUT >= 64 ? 0 : COUT == 32 ? 1 : 2;
-    constexpr unsigned kSwzMask = COUT >= 64 ? 15u : COUT == 32 ? 7u : 3u;
-    unsigned char *acc_bytes = reinterpret_cast<unsigned char *>(s_acc + ts * (TM + 1) * COUT);  // this wave's tile copy
+    unsigned char *acc_bytes = reinterpret_cast<unsigned char *>(s_acc + ts * L.acc_copy);  // this wave's tile copy
     const unsigned slot0 = (unsigned)(cb >> 2) + (unsigned)lq;  // 16-byte slot of this lane's 4 channels in block nw = 0
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
-    unsigned short *items = s_items + wave * kMaxItems;
+    unsigned short *items = s_items + wave * L.item_slot;
 
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
-    const int row0 = r_begin + chunk * chunk_rows;
-    const int n_rows = (r_end - row0) < chunk_rows ? (r_end - row0) : chunk_rows;
-    if (n_rows <= 0) break;
-    // ---- stage the prefetched slice, clear the accumulators
-#pragma unroll
-    for (int i = 0; i < NPRE; ++i) {
-        const int t = tid + i * 256;
-        const int r = t % TM;
-        if (t < K * TM) s_list[t] = r < n_rows ? pre[i] : -1;
-    }
-    // Accumulator tile.  For COUT <= 64 the tile starts from bias + residual instead of zero: the epilogue then has no global
-    // load left (it used to issue one dependent residual load per 256 rows x 4 channels -- 4 to 8 exposed memory round trips per
-    // chunk, as long as the chunk's whole MFMA loop on the 32-channel layers: the "unexplained" 47 % dependency stall of round 2).
-    // All loads of a chunk go out back to back here and land during the list staging.  (128 columns: 64 registers per thread
-    // would be needed; that layer is MFMA-bound and keeps the epilogue form.)
-    constexpr bool kInitAcc = COUT <= 64;
-    if constexpr (kInitAcc) {
-        constexpr int C4i = COUT / 4, NINIT = TM * C4i / 256;
-        static_assert(TM * C4i % 256 == 0, "whole passes");
-        float4 iv[NINIT];
-#pragma unroll
-        for (int i = 0; i < NINIT; ++i) {
-            const int t = tid + i * 256, c4 = t % C4i;
-            iv[i] = bias ? reinterpret_cast<const float4 *>(bias)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (residual) {
-            float4 rv[NINIT];
-#pragma unroll
-            for (int i = 0; i < NINIT; ++i) {
-                const int t = tid + i * 256, r = t / C4i, c4 = t - r * C4i;
-                const int rr = r < n_rows ? r : n_rows - 1;  // (clamped address, selected on use)
-                rv[i] = reinterpret_cast<const float4 *>(residual + (int64_t)(row0 + rr) * COUT)[c4];
-            }
-#pragma unroll
-            for (int i = 0; i < NINIT; ++i) { iv[i].x += rv[i].x; iv[i].y += rv[i].y; iv[i].z += rv[i].z; iv[i].w += rv[i].w; }
-        }
-#pragma unroll
-        for (int i = 0; i < NINIT; ++i) {
-            const int t = tid + i * 256, r = t / C4i, c4 = t - r * C4i;
-            const int ts4 = r * C4i + (c4 ^ (int)(((unsigned)r >> kSwzShift) & kSwzMask));
-            reinterpret_cast<float4 *>(s_acc)[ts4] = r < n_rows ? iv[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        // the scratch row of copy 0 and the other tile copies start from zero
-        for (int t = TM * C4i + tid; t < TS * (TM + 1) * COUT / 4; t += 256) reinterpret_cast<float4 *>(s_acc)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-        for (int t = tid; t < TS * (TM + 1) * COUT / 4; t += 256) reinterpret_cast<float4 *>(s_acc)[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (tid < 16) s_pad[tid] = kPad;
+    int row0, n_rows;
+    if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
+    sk::stage_chunk<TM, COUT, TS, 16>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
     __syncthreads();
     if (chunk == 0) FD_T(1);
-    // ---- in-place compaction: wave w takes taps w, w+4, ...; tails are filled with kPad
-    for (int k = wave; k < K; k += 4)
-    {
-#pragma unroll
-        for (int wr = 0; wr < WR; ++wr) {
-            const int base = k * TM + wr * RW;
-            int count = 0;
-            int v[(RW + 63) / 64];
-#pragma unroll
-            for (int h = 0; h < (RW + 63) / 64; ++h) {
-                const int r = h * 64 + lane;
-                v[h] = (r < RW) ? s_list[base + r] : -1;
-            }
-#pragma unroll
-            for (int h = 0; h < (RW + 63) / 64; ++h) {
-                const int r = h * 64 + lane;
-                if (r < RW) s_list[base + r] = kPad;
-            }
-#pragma unroll
-            for (int h = 0; h < (RW + 63) / 64; ++h) {
-                const int r = h * 64 + lane;
-                const unsigned long long m = __ballot(v[h] >= 0);
-                const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-                if (v[h] >= 0) s_list[base + pos] = (v[h] << 8) | (wr * RW + r);
-                count += __popcll(m);
-            }
-            if (lane == 0) s_cnt[k * 4 + wr] = (unsigned char)count;
-        }
-    }
+    sk::compact_taps<TM, WR>(s_list, s_cnt, K);
     __syncthreads();
     if (chunk == 0) FD_T(2);
     // the next chunk's slice travels while this chunk computes
-    if (chunk + 1 < n_chunks) fetch_slice(row0 + chunk_rows);
-
-    // ---- flattened work list of this wave: one item = 16 compacted pairs of one tap, code = (tap << 3) | group
-    int n_items;
-    unsigned long long tapmask;
-    {
-        const int ng = (lane < K && (lane % TS) == ts) ? ((int)s_cnt[lane * 4 + wr] + 15) >> 4 : 0;
-        tapmask = __ballot(ng > 0);
-        int inc = ng;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int u = __shfl_up(inc, off);
-            if (lane >= off) inc += u;
-        }
-        n_items = __builtin_amdgcn_readfirstlane(__shfl(inc, 63));
-        for (int g = 0; g < ng; ++g) items[inc - ng + g] = (unsigned short)((lane << 3) | g);
-    }
-    // wave-local LDS hand-off (items written above are read below by other lanes of the same wave)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (chunk + 1 < n_chunks) sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, row0 + chunk_rows);
+    const int n_items = sk::build_items<TS, 16>(s_cnt, items, K, ts, wr);
 
     // ring of DEPTH prefetched items.  Gathers are buffer loads with hardware bounds checking: a padding lane / a
     // slot past the end of the work list gets an out-of-range offset and reads zeros, so prefetch AND compute are
@@ -259,21 +142,9 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     //                              drop the read altogether but ds_add_f32 measured 2-4x slower for the whole kernel.)
     // A wave owns its accumulator elements and LDS operations of a wave execute in order, so the sums are formed in a
     // fixed order (taps ascending): deterministic.
-    auto stage_a0 = [&](int it) -> int { return (int)items[it < n_items ? it : 0]; };
-    auto stage_a1 = [&](int it, int code_v, int &kk, int &e) {
-        const bool v = it < n_items;  // uniform (n_items is in a scalar register)
-        const int code = __builtin_amdgcn_readfirstlane(code_v);
-        const int ks = v ? (code >> 3) : 0;
-        kk = v ? ks : -1;
-        // past the end of the work list the (scalar) list pointer selects a block of 16 padding entries: no per-lane select
-        const int *lst = v ? s_list + ks * TM + wr * RW + ((code & 7) << 4) : s_pad;
-        e = lst[lrow];
-    };
-    auto gather_offset = [&](int e) -> unsigned {
-        // byte offset of the input row = (e >> 8) * CIN * 4, computed on the masked entry without a multiply
-        const unsigned hi = (unsigned)e & 0xffffff00u;
-        return (CIN >= 64 ? hi << (CIN == 128 ? 1 : 0) : hi >> (CIN == 32 ? 1 : 2)) + (unsigned)(lq * 16);
-    };
+    auto stage_a0 = [&](int it) -> int { return sk::stage_a0(items, n_items, it); };
+    auto stage_a1 = [&](int it, int code_v, int &kk, int &e) { sk::stage_a1<TM, WR, 16>(s_list, s_pad, n_items, wr, lrow, it, code_v, kk, e); };
+    auto gather_offset = [&](int e) -> unsigned { return sk::entry_row_bytes<CIN>(e) + (unsigned)(lq * 16); };
     auto gather_chunk = [&](unsigned voff, int c) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 64, 0, 0); };
     auto load_b = [&](int k, float4(&dst)[NC][NBW]) {
         const float4 *wk = wp + ((int64_t)k * NC * NB + wc * NBW) * 64 + lane;
@@ -327,11 +198,10 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
         for (int d = 0; d < DEPTH; ++d) {
             // accumulator row of this lane's pair (the row field of a padding entry is the scratch row TM): one swizzled
             // 16-byte slot per 16-column block
-            const unsigned arow = (unsigned)row_r[d] & 255u;
-            const unsigned abase = arow << kRowShift, aswz = (arow >> kSwzShift) & kSwzMask;
+            const unsigned arow = sk::entry_local_row(row_r[d]);
             unsigned aoff[NBW];
 #pragma unroll
-            for (int nw = 0; nw < NBW; ++nw) aoff[nw] = abase + (((slot0 + 4u * nw) ^ aswz) << 4);
+            for (int nw = 0; nw < NBW; ++nw) aoff[nw] = sk::acc_slot_bytes<COUT>(arow, slot0 + 4u * nw);
             // The old accumulator values are requested first and are the C operand of the MFMA chain: the matrix pipe
             // does the accumulation and D goes back to LDS untouched -- no vector-ALU work on the accumulators at all
             // (VALU instructions of one wave barely overlap the MFMAs of the other waves of its SIMD, so every VALU
@@ -392,40 +262,11 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     if (chunk == 0) FD_T(4);
     __syncthreads();
     if (chunk == 0) FD_T(5);
-    // ---- epilogue: whole chunk, float4 per thread, rows contiguous in global memory (swizzled slots in LDS)
-    constexpr int C4 = COUT / 4;
-    for (int t = tid; t < n_rows * C4; t += 256) {
-        const int r = t / C4, c4 = t - r * C4;
-        const int row = row0 + r;
-        const int ts4 = r * C4 + (c4 ^ (int)(((unsigned)r >> kSwzShift) & kSwzMask));
-        float4 v = reinterpret_cast<const float4 *>(s_acc)[ts4];
-#pragma unroll
-        for (int q = 1; q < TS; ++q) {
-            const float4 v2 = reinterpret_cast<const float4 *>(s_acc + q * (TM + 1) * COUT)[ts4];
-            v.x += v2.x; v.y += v2.y; v.z += v2.z; v.w += v2.w;
-        }
-        if constexpr (!kInitAcc) {
-            if (bias) {
-                const float4 bv = reinterpret_cast<const float4 *>(bias)[c4];
-                v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-            }
-            if (residual) {
-                const float4 rv = reinterpret_cast<const float4 *>(residual + (int64_t)row * COUT)[c4];
-                v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-            }
-        }
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        reinterpret_cast<float4 *>(out + (int64_t)row * COUT)[c4] = v;
-    }
+    sk::epilogue<TM, COUT, TS>(s_acc, bias, residual, relu, out, row0, n_rows);
     __syncthreads();  // the next chunk re-uses the list and the accumulator tile
     if (chunk == 0) FD_T(6);
     }  // chunk loop
     FD_T(7);
-}
-
-constexpr size_t lds_bytes(int tm, int cout) {
-    return sizeof(int) * kMaxTaps * tm + sizeof(unsigned short) * 4 * kMaxTaps * (tm / 16) + 112 + 64 +
-           sizeof(float) * (tm + 1) * cout * (cout == 32 || cout == 64 ? 2 : 1);
 }
 
 // LDS request of one workgroup.  Occupancy is not a lever here: MFMA and non-MFMA instructions of the waves sharing a
@@ -433,7 +274,7 @@ constexpr size_t lds_bytes(int tm, int cout) {
 // layers two workgroups per CU beat the three that would fit (300 -> 278 us: less contention in the gather path), so
 // their request is rounded up to just over a third of the CU's 160 KB.
 inline size_t lds_request(int cin, int cout, int tm) {
-    const size_t lds = lds_bytes(tm, cout);
+    const size_t lds = (size_t)sk::layout(tm, cout, tap_splits(cout), 16).bytes;
     const size_t pad = (size_t)fd::tuning(fd::kTuneV2LdsPad);  // occupancy experiments
     if (pad) return lds + pad;
     return (cin == 64 && cout == 64 && tm == 128 && lds < 56 * 1024) ? (size_t)56 * 1024 : lds;
@@ -455,11 +296,7 @@ int launch_compact(const float *in, const void *wp, const float *bias, const flo
         return 0;
     }
     int rows_per = 0;
-    if (!ranges) {  // equal row counts (multiples of 16): n_ranges == 0 -> one TM-row tile per workgroup
-        if (n_ranges <= 0) n_ranges = (n_out + TM - 1) / TM;
-        rows_per = (((n_out + n_ranges - 1) / n_ranges) + 15) & ~15;
-        if (!n_out_dev) n_ranges = (n_out + rows_per - 1) / rows_per;  // (with a device count the kernel makes the split over n_ranges)
-    }
+    if (!ranges) sk::equal_rows_split(n_out, TM, n_out_dev != nullptr, n_ranges, rows_per);
     hipLaunchKernelGGL(kern, dim3((unsigned)n_ranges), dim3(256), lds_req, stream, in, (const float4 *)wp, bias, residual, relu, nbr, nbr_stride, K,
                        n_out, n_out_dev, out, in_bytes, ranges, rows_per);
     return 1;
@@ -668,8 +505,7 @@ namespace fd {
 int spconv_f32_compact_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr,
                                 int64_t nbr_stride, int K, int64_t n_in_bound, int n_out, const int *n_out_dev, int cin, int cout, float *out,
                                 const int *ranges, int n_ranges, hipStream_t stream) {
-    // (input row << 8 | local row) must fit an int32 and the feature matrix a 31-bit buffer range
-    if (n_in_bound >= (1ll << 23) || n_in_bound * cin * 4 >= (1ll << 31)) return 0;
+    if (!sk::entries_fit(n_in_bound, cin)) return 0;
     const unsigned in_bytes = (unsigned)(n_in_bound * cin * 4);
     const int dsel = fd::tuning(fd::kTuneV2Depth), tsel = fd::tuning(fd::kTuneV2TM);  // tuning overrides
 #define FD_LAUNCH(CI, CO, T, D) \
