@@ -225,13 +225,10 @@ class VoxelNet(SingleStageDetector):
         mark_stage("index")
         # every row of the level-0 index is exactly one voxel, and fd_rows_place writes all cpad channels of it: no fill
         feats0 = torch.empty((max(idx[0].n, 1), cpad), dtype=bb.compute_dtype, device=dev)[: idx[0].n]
-        L = hip_ops._lib.load()
         i0 = idx[0]
         for b in range(B if i0.n > 0 else 0):  # (nothing to place when every cloud of the batch is empty)
             sl = slice(b * max_voxels, (b + 1) * max_voxels)
-            hip_ops.check(L.fd_rows_place(hip_ops._p(i0.words), hip_ops._p(i0.prefix), i0.B, i0.D, i0.H, i0.W, hip_ops._p(coors[sl]),
-                                          hip_ops._p(nvox[b:b + 1]), max_voxels, hip_ops._p(mean[sl]), cpad, hip_ops._p(feats0), cpad,
-                                          hip_ops._DT[bb.compute_dtype], hip_ops._stream()), "fd_rows_place")
+            hip_ops.rows_place(i0, coors[sl], mean[sl], cpad, bb.compute_dtype, n_dev=nvox[b:b + 1], out=feats0)
         graph = None if (bev_map is not None or _NO_GRAPH or static) else self._dense_graph(B, idx[4], dev)
         if graph is not None:
             # neck + head have static shapes: replay them as one hipGraph (one launch instead of ~25-60)

@@ -333,6 +333,27 @@ def rows_permute(src, row_of, c_dst, dtype=torch.float32, n_rows=None, n_dev=Non
     return dst
 
 
+def rows_place(index, coords, src, c_dst, dtype=torch.float32, n_dev=None, out=None):
+    """fd_rows_place: dst[row of coords[i] in ``index``][:] = src[i][:] (channels >= src.shape[1] zeroed) for the first
+    min(len(coords), n_dev[0]) voxels; a coordinate that is not in the index is skipped.  ``out``: pre-allocated [rows, c_dst]
+    destination of ``dtype`` (otherwise zeros [index.n, c_dst]); rows that no voxel maps to are left as they are."""
+    L = _lib.load()
+    coords = _dev(coords, "coords", torch.int32)
+    src = _dev(src, "src", torch.float32)
+    if out is None:
+        out = torch.zeros((max(index.n, 1), c_dst), dtype=dtype, device=src.device)[: index.n]
+    _dev(out, "out", dtype)
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise FutureDetHipError("rows_place: coords must be [n, 4] (b, z, y, x), got %s" % (tuple(coords.shape),))
+    if src.dim() != 2 or src.shape[0] < coords.shape[0]:
+        raise FutureDetHipError("rows_place: src must be [n, c_src] with a row per coordinate")
+    if out.dim() != 2 or out.shape[1] != c_dst or index.n is None or out.shape[0] < index.n:
+        raise FutureDetHipError("rows_place: out must be [rows >= index.n, %d] (finalised index), got %s" % (c_dst, tuple(out.shape)))
+    check(L.fd_rows_place(_p(index.words), _p(index.prefix), index.B, index.D, index.H, index.W, _p(coords), _p(n_dev),
+                          coords.shape[0], _p(src), src.shape[1], _p(out), c_dst, _DT[dtype], _stream()), "fd_rows_place")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ sparse conv
 def pack_spconv_weight(w_kio, dtype=torch.float32):
     """[K, Cin, Cout] float32 (host or device) -> fragment-ordered packed weights on the same device."""

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from front_end_ref import RULEBOOK_GEOMS
 from parity_util import assert_close, attribute_detection_diffs, greedy_violations, nms_layout, rel_err, report
 
 pytestmark = pytest.mark.gpu
@@ -71,8 +72,8 @@ def _random_sparse(rng, B, D, H, W, p, cin):
     return idx, feats
 
 
-GEOMS = [((3, 3, 3), (1, 1, 1), (1, 1, 1), True), ((3, 3, 3), (2, 2, 2), (1, 1, 1), False),
-         ((3, 3, 3), (2, 2, 2), (0, 1, 1), False), ((3, 1, 1), (2, 1, 1), (0, 0, 0), False)]
+# the backbone's four geometries, then the rest of the range fd_rulebook / fd_index_downsample accept (front_end_ref.py)
+GEOMS = RULEBOOK_GEOMS
 
 
 @pytest.mark.parametrize("geom", GEOMS)
