@@ -20,6 +20,7 @@ from collections import defaultdict
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import hip_ops
 from .nn_utils import Sequential, deform_conv2d_v1, kaiming_init, weights_version
@@ -116,6 +117,25 @@ class DeformConv(nn.Module):
         return deform_conv2d_v1(x, offset, self.weight, self.deformable_groups, self.padding)
 
 
+class _DeformAdaptFunction(torch.autograd.Function):
+    """(x [B,H,W,64], offsets [B,H,W,144], w_cls, w_reg [64,64,3,3]) -> y [B,H,W,128] = [ReLU(DCN_cls(x)) | ReLU(DCN_reg(x))], fp32 on the
+    device.  Saves x, the offsets, the weights and y (the ReLU mask); the backward re-samples."""
+
+    @staticmethod
+    def forward(ctx, x, offsets, w_cls, w_reg):
+        y = hip_ops.deform_adapt_nhwc(x, hip_ops.pack_deform_adapt_device(w_cls, w_reg), offsets=offsets)
+        ctx.save_for_backward(x, offsets, w_cls, w_reg, y)
+        return y
+
+    @staticmethod
+    @once_differentiable  # the kernels are not differentiable themselves: a double backward raises here
+    def backward(ctx, dy):
+        x, offsets, w_cls, w_reg, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, doff, dw = hip_ops.deform_adapt_backward(x, offsets, w_cls, w_reg, y, dy.contiguous(), need=(need[0], need[1], need[2] or need[3]))
+        return dx, doff, dw[0] if need[2] else None, dw[1] if need[3] else None
+
+
 class FeatureAdaption(nn.Module):
     """center_head.py:40-78: ReLU(DeformConv(x, conv_offset(x))), conv_offset a 1x1 conv to dg * 2 * k * k offset channels (zero-initialised)."""
 
@@ -145,9 +165,25 @@ class DCNSepHead(nn.Module):
         self.task_head = SepHead(in_channels, heads, head_conv=head_conv, bn=bn, final_kernel=final_kernel)
 
     def forward_modules(self, x):
-        ret = self.task_head(self.feature_adapt_reg(x))
-        ret["hm"] = self.cls_head(self.feature_adapt_cls(x))
+        if self.training and x.is_cuda:
+            a_cls, a_reg = self._adapt_pair_train(x)
+        else:
+            a_cls, a_reg = self.feature_adapt_cls(x), self.feature_adapt_reg(x)
+        ret = self.task_head(a_reg)
+        ret["hm"] = self.cls_head(a_cls)
         return ret
+
+    def _adapt_pair_train(self, x):
+        """Both FeatureAdaption modules in training on the device: the offsets from the modules' own 1x1 conv_offset (torch, like every
+        other head convolution in training), the deformable pair as one fd_deform_adapt_nhwc launch whose backward is
+        fd_deform_adapt_backward.  Nothing of im2col size is computed or saved.  fp32 only: CenterHead.forward_modules refuses a bf16
+        compute_dtype, and hip_ops rejects any other tensor dtype."""
+        fc, fr = self.feature_adapt_cls, self.feature_adapt_reg
+        offsets = torch.cat([fc.conv_offset(x), fr.conv_offset(x)], 1).permute(0, 2, 3, 1).contiguous()
+        y = _DeformAdaptFunction.apply(x.permute(0, 2, 3, 1).contiguous(), offsets, fc.conv_adaption.weight, fr.conv_adaption.weight)
+        y = y.permute(0, 3, 1, 2)
+        c = x.shape[1]
+        return y[:, :c], y[:, c:]
 
     def forward(self, x):
         return self.forward_modules(x)
@@ -244,6 +280,9 @@ class CenterHead(nn.Module):
     # ----------------------------------------------------------------------------------------------- forward
     def forward_modules(self, x, bev_map=None):
         ret_dicts = []
+        if self.dcn_head and self.training and x.is_cuda and self.compute_dtype != torch.float32:
+            raise NotImplementedError("CenterHead(dcn_head=True): training runs in fp32 only; the %s head is inference-only (set "
+                                      "compute_dtype = torch.float32 to train)" % self.compute_dtype)
         x = self.shared_conv(x)
         if self.bev_map:
             x = x + self.bev_conv(bev_map)

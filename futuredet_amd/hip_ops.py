@@ -677,6 +677,44 @@ def deform_adapt_nhwc(x, wpk, off_w=None, off_b=None, offsets=None, out=None):
     return out
 
 
+def _adapt_weight(w, name):
+    w = _dev(w.detach(), name, torch.float32)
+    if tuple(w.shape) != (64, 64, 3, 3):
+        raise FutureDetHipError("fd_deform_adapt: %s must be [64, 64, 3, 3], got %s" % (name, tuple(w.shape)))
+    return w
+
+
+def pack_deform_adapt_device(w_cls, w_reg):
+    """The fp32 packed conv_adaption weights of pack_deform_adapt, from device weights with no host round trip
+    (fd_deform_adapt_pack_weight_device; byte-identical to the host packer)."""
+    L = _lib.load()
+    wc, wr = _adapt_weight(w_cls, "w_cls"), _adapt_weight(w_reg, "w_reg")
+    out = torch.empty((L.fd_deform_adapt_packed_weight_bytes(0),), dtype=torch.uint8, device=wc.device)
+    check(L.fd_deform_adapt_pack_weight_device(_p(wc), _p(wr), _p(out), _stream()), "fd_deform_adapt_pack_weight_device")
+    return out
+
+
+def deform_adapt_backward(x, offsets, w_cls, w_reg, y, dy, need=(True, True, True)):
+    """Gradients of deform_adapt_nhwc(x, pack(w_cls, w_reg), offsets=offsets) = y under dy (fd_deform_adapt_backward), all fp32 NHWC:
+    -> (dx [B,H,W,64], doffsets [B,H,W,144], dw [2,64,64,3,3]); an entry of ``need`` = (dx, doffsets, dw) that is False gives None.
+    doffsets and dw are bit-identical from run to run; dx is summed with atomic adds."""
+    L = _lib.load()
+    x = _dev(x, "x", torch.float32)
+    B, H, W, C = x.shape
+    for t, name, ch in ((offsets, "offsets", 144), (y, "y", 2 * C), (dy, "dy", 2 * C)):
+        _dev(t, name, torch.float32)
+        if tuple(t.shape) != (B, H, W, ch):
+            raise FutureDetHipError("%s must be [B, H, W, %d], got %s" % (name, ch, tuple(t.shape)))
+    wc, wr = _adapt_weight(w_cls, "w_cls"), _adapt_weight(w_reg, "w_reg")
+    dx = torch.empty_like(x) if need[0] else None
+    doff = torch.empty_like(offsets) if need[1] else None
+    dw = torch.empty((2, 64, 64, 3, 3), dtype=torch.float32, device=x.device) if need[2] else None
+    ws = workspace.get("deform_adapt_backward", L.fd_deform_adapt_backward_workspace_bytes(B, H, W), x.device)
+    check(L.fd_deform_adapt_backward(_p(x), _p(offsets), _p(wc), _p(wr), _p(y), _p(dy), B, H, W, C, _p(dx), _p(doff), _p(dw), _p(ws), ws.numel(),
+                                     _stream()), "fd_deform_adapt_backward")
+    return dx, doff, dw
+
+
 def make_decode_cfg(H, W, test_cfg, hm_channels=1, group_radius=None):
     """``hm_channels`` > 1: the score of a cell is the maximum over that many heat-map channels (CenterHead's ``classify``
     mode, center_head.py:589-595: torch.max(hm, dim=1) before the sigmoid).  ``group_radius``: test_cfg.circular_nms

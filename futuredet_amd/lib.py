@@ -132,6 +132,10 @@ SIGNATURES = {
     "fd_deform_adapt_packed_weight_bytes": (c_size_t, [c_int]),
     "fd_deform_adapt_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "fd_deform_adapt_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fd_deform_adapt_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fd_deform_adapt_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_deform_adapt_pack_weight_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fd_spconv_wgrad_workspace_bytes": (c_size_t, [c_int, c_i64, c_int, c_int]),
     "fd_spconv_wgrad": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),

@@ -461,6 +461,23 @@ int fd_deform_adapt_pack_weight(const float *w_cls_oihw_host, const float *w_reg
 int fd_deform_adapt_nhwc(const void *x, int B, int H, int W, int C, int bf16, const float *off_w, const float *off_b, const float *offsets,
                          const void *wpacked, void *y, fd_stream_t stream);
 
+/* Training of the pair (fd_deform_conv_grad.hip): the reference's deformable_col2im / deformable_col2im_coord
+ * (deform_conv_cuda_kernel.cu) for the shapes above, fp32 only.  Purely additive: fd_abi_version() stays 8.
+ * Inputs: x [B,H,W,64], offsets [B,H,W,144] as the forward reads them, the two conv_adaption weights [64,64,3,3] (OIHW) in
+ * DEVICE memory, the forward's output y [B,H,W,128] (only its sign is used: the ReLU mask y > 0) and dy [B,H,W,128].
+ * Outputs, each skipped when NULL: dx [B,H,W,64] (zeroed here on the stream, then fp32 atomic adds: equal from run to run only
+ * up to the summation order), doffsets [B,H,W,144] and dw [2][64][64][3][3] (cls, reg; OIHW) -- both bit-identical from run to
+ * run.  At an integer sample coordinate the offset gradient is the right-hand derivative (get_coordinate_weight).  The call
+ * neither allocates nor synchronises; workspace of fd_deform_adapt_backward_workspace_bytes(B, H, W) bytes (0 = bad shape).
+ * All tensor pointers and the workspace 16-byte aligned.
+ * fd_deform_adapt_pack_weight_device: the fp32 form of fd_deform_adapt_pack_weight from device weights into device memory,
+ * byte-identical to the host packer's output (fd_deform_adapt_packed_weight_bytes(0) bytes). */
+size_t fd_deform_adapt_backward_workspace_bytes(int B, int H, int W);
+int fd_deform_adapt_backward(const float *x, const float *offsets, const float *w_cls_oihw, const float *w_reg_oihw, const float *y, const float *dy,
+                             int B, int H, int W, int C, float *dx, float *doffsets, float *dw, void *workspace, size_t workspace_bytes,
+                             fd_stream_t stream);
+int fd_deform_adapt_pack_weight_device(const float *w_cls_oihw, const float *w_reg_oihw, void *wpacked, fd_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Training: the backward pass of the fp32 sparse convolution (fd_spconv_grad.hip) -- spconv 1.0's indice_conv_backward /
  * indice_subm_conv_backward (gradients of scn.py:99-141 under loss.backward()).  Purely additive: fd_abi_version() stays 8.
