@@ -321,6 +321,144 @@ def gen_iou():
     save("iou.npz", a=a, b=b, iou=iou)
 
 
+IOU_EDGE_FAMILIES = ("identical", "axis0", "contain", "quarter", "nearpar", "extents", "range_edge", "threshold")
+
+
+def _iou_edge_pairs():
+    """-> (a [n,7], b [n,7], family index [n]): pairs on which the rotated IoU's sign tests, its 1e-2 inside margin, its degenerate-ratio
+    branch and the tie order of its sort decide the answer"""
+    rng = np.random.default_rng(47)
+    A, B, F = [], [], []
+
+    def box(x, y, dx, dy, yaw):
+        return np.array([x, y, 0.0, dx, dy, 1.5, yaw], np.float32)
+
+    def add(fam, a, b):
+        A.append(a); B.append(b); F.append(IOU_EDGE_FAMILIES.index(fam))  # noqa: E702
+
+    def rand_box(cx=0.0, cy=0.0, spread=20.0):
+        return box(cx + rng.uniform(-spread, spread), cy + rng.uniform(-spread, spread), rng.uniform(1.5, 5), rng.uniform(1.0, 2.5), rng.uniform(-2 * np.pi, 2 * np.pi))
+
+    # identical: the same box twice
+    for yaw in [0.0, np.pi / 2, -np.pi / 2, np.pi, 2 * np.pi, np.pi / 4, 1e-7, -1e-7, 1e-4]:
+        a = rand_box()
+        a[6] = yaw
+        add("identical", a, a.copy())
+    for _ in range(40):
+        a = rand_box()
+        add("identical", a, a.copy())
+    # axis0: shared edges, corner contact, gaps inside and outside the 1e-2 margin
+    for dx in [0, 1, 2, 3, 3.99, 4, 4.01, 4.02, 5]:
+        for dy in [0, 1, 1.99, 2, 2.01, 2.02, 3]:
+            add("axis0", box(0, 0, 4, 2, 0), box(dx, dy, 4, 2, 0))
+    # contain: a small box strictly inside a large one (half diagonal of the small one + its offset < the large one's smaller half extent)
+    for k in range(60):
+        big = rand_box()
+        big[3:5] = rng.uniform(4, 6), rng.uniform(2, 3)
+        off = rng.uniform(-0.3, 0.3, 2)
+        small = box(big[0] + off[0], big[1] + off[1], rng.uniform(0.3, 0.8), rng.uniform(0.2, 0.5), rng.uniform(-2 * np.pi, 2 * np.pi))
+        add("contain", *((big, small) if k % 2 else (small, big)))
+    # quarter: a box against itself turned by quarter turns (float32 arithmetic), and against the same rectangle written with extents swapped
+    for k in range(30):
+        a = rand_box()
+        if k < 6:
+            a[6] = [0.0, np.pi / 4, np.pi / 2, 1.0, -np.pi, 1e-4][k]
+        if k % 3 == 0:
+            a[4] = a[3]  # squares: a quarter turn maps the box onto itself
+        for q in range(1, 5):
+            b = a.copy()
+            b[6] = a[6] + np.float32(q) * np.float32(np.pi / 2)
+            add("quarter", a, b)
+        b = a.copy()
+        b[3], b[4] = a[4], a[3]
+        b[6] = a[6] + np.float32(np.pi / 2)
+        add("quarter", a, b)
+    # nearpar: nearly parallel edges, the second box shifted along the box's own long axis
+    for yaw in [0.0, 0.3, np.pi / 4, -1.2, 2.9]:
+        for dyaw in [1e-7, 1e-6, 1e-5, 1e-4, 1e-3, 1e-2]:
+            for shift in [0.0, 0.5, 3.9]:
+                a = box(rng.uniform(-20, 20), rng.uniform(-20, 20), 4, 2, yaw)
+                b = a.copy()
+                b[0] = a[0] + np.float32(shift * np.cos(yaw))
+                b[1] = a[1] + np.float32(shift * np.sin(yaw))
+                b[6] = a[6] + np.float32(dyaw)
+                add("nearpar", a, b)
+    # extents: vanishing and huge widths / lengths against normal boxes (the reference's IoU exceeds 1 on some: that is the expected value)
+    for dx, dy in [(0, 0), (0, 2), (4, 0), (1e-3, 1e-3), (1e-3, 2), (4, 1e-3), (1e-6, 5), (5, 1e-6), (100, 100), (100, 0.01), (0.01, 100), (100, 2)]:
+        for yaw in [0.0, 0.4, np.pi / 2]:
+            for ox, oy, nyaw in [(0, 0, 0.0), (0.5, 0.25, 0.0), (1.0, 0.0, 0.7)]:
+                odd = box(3 + ox, -2 + oy, dx, dy, yaw)
+                normal = box(3, -2, 4, 2, nyaw)
+                add("extents", *((odd, normal) if (len(A) % 2) else (normal, odd)))
+    # ... and against each other a few millimetres apart: the 1e-2 margin takes corners of both into the polygon, whose area then exceeds both boxes'
+    for dx, dy in [(0, 0), (1e-3, 1e-3), (1e-3, 2), (1e-6, 5), (0, 2)]:
+        for ox, oy in [(0, 0), (5e-3, 0), (5e-3, 5e-3), (0, 8e-3)]:
+            for yaw in [0.0, 0.4]:
+                add("extents", box(3, -2, dx, dy, yaw), box(3 + ox, -2 + oy, dx, dy, yaw))
+    # range_edge: ordinary overlapping pairs at the largest coordinates the decode lets through (post_center_limit_range +-61.2)
+    for c in (50.0, 60.0):
+        for sx in (-1, 1):
+            for sy in (-1, 1):
+                for _ in range(8):
+                    a = rand_box(sx * c, sy * c, 0.5)
+                    b = a.copy()
+                    b[:2] += rng.normal(0, 0.5, 2).astype(np.float32)
+                    b[3:5] *= rng.uniform(0.8, 1.25, 2).astype(np.float32)
+                    b[6] += np.float32(rng.normal(0, 0.3))
+                    add("range_edge", a, b)
+    # threshold: equal yaw-0 boxes shifted along one axis by a multiple of 2^-12 (every corner exact in float32); a shift s along an extent e
+    # gives IoU (e - s) / (e + s): the shifts nearest to IoU 0.190, 0.191, ... 0.210
+    for ex, ey, axis in [(4, 2, 0), (4, 2, 1), (2, 2, 0)]:
+        e = (ex, ey)[axis]
+        for t in range(-10, 11):
+            want = 0.2 + 1e-3 * t
+            s = np.round(e * (1 - want) / (1 + want) * 4096) / 4096
+            b = box(1, -3, ex, ey, 0)
+            b[axis] += np.float32(s)
+            add("threshold", box(1, -3, ex, ey, 0), b)
+    return np.stack(A), np.stack(B), np.array(F, np.int8)
+
+
+def gen_iou_edges():
+    """Degenerate pairs through the reference's own compiled iou3d_cpu.cpp, pair by pair.  Asserts (a) that oracle/fd_oracle.c reproduces the
+    compiled reference bit for bit on every pair, and (b) that the value is stable when either yaw moves to a neighbouring float32 (the stand-in
+    for the last-ulp difference between host and device sinf / cosf / atan2f): pairs whose nine values spread by more than
+    1e-5 * max(1, |iou|) are dropped, at most 2 % of all pairs and 10 % of a family."""
+    a, b, fam = _iou_edge_pairs()
+    n = len(a)
+
+    def pairwise(fn, a, b):
+        return np.array([fn(a[i:i + 1], b[i:i + 1])[0, 0] for i in range(len(a))], np.float32)
+
+    ref = pairwise(oops.ref_boxes_iou_bev, a, b)
+    assert np.all(np.isfinite(ref)), "non-finite reference IoU: out of scope, change the family"
+    mine = pairwise(oops.boxes_iou_bev, a, b)
+    equal = mine.view(np.uint32) == ref.view(np.uint32)
+    print("iou_edges: restatement bit-equal to the compiled reference on %d of %d pairs" % (int(equal.sum()), n))
+    assert equal.all(), [(IOU_EDGE_FAMILIES[fam[i]], a[i].tolist(), b[i].tolist(), float(ref[i]), float(mine[i])) for i in np.nonzero(~equal)[0][:5]]
+    vals = []
+    for da in (-np.inf, 0, np.inf):
+        for db in (-np.inf, 0, np.inf):
+            a2, b2 = a.copy(), b.copy()
+            if da:
+                a2[:, 6] = np.nextafter(a[:, 6], np.float32(da))
+            if db:
+                b2[:, 6] = np.nextafter(b[:, 6], np.float32(db))
+            vals.append(pairwise(oops.boxes_iou_bev, a2, b2).astype(np.float64))
+    vals = np.stack(vals)
+    spread = vals.max(0) - vals.min(0)
+    keep = spread <= 1e-5 * np.maximum(1.0, np.abs(ref))
+    for f, name in enumerate(IOU_EDGE_FAMILIES):
+        m = fam == f
+        dropped = int((m & ~keep).sum())
+        print("  %-10s %3d pairs, %d dropped, largest kept spread %.2e, IoU range [%.6g, %.6g]" %
+              (name, int(m.sum()), dropped, spread[m & keep].max(), ref[m].min(), ref[m].max()))
+        assert dropped <= 0.10 * m.sum(), "family %s: %d of %d pairs unstable -- change the family's parameters, not the cap" % (name, dropped, m.sum())
+    print("iou_edges: dropped %d of %d pairs (%.2f %%), largest spread among the kept %.2e" % (int((~keep).sum()), n, 100.0 * (~keep).mean(), spread[keep].max()))
+    assert (~keep).sum() <= 0.02 * n
+    save("iou_edges.npz", a=a[keep], b=b[keep], iou=ref[keep], family=fam[keep], family_names=np.array(IOU_EDGE_FAMILIES))
+
+
 def gen_backbone():
     """The reference's UNMODIFIED scn.py (SpMiddleResNetFHD) driven over oracle/spconv_api.py: pins topology
     (layer order, which convs carry bias, indice_key reuse, residual wiring, dense() view), not spconv maths."""
@@ -862,7 +1000,7 @@ if __name__ == "__main__":
     install_shims()
     sys.path.insert(0, REF)
     which = sys.argv[1:] or ["voxelizer", "configs", "dense", "predict", "iou", "backbone", "sweeps", "pillars", "forecast", "forecast2",
-                            "forecast_edges"]
+                            "forecast_edges", "iou_edges"]
     if len(which) > 1:
         # one generator per process: each installs the import shims it needs for the reference modules it imports, and the
         # shims of one (det3d.datasets stand-ins of the forecast generators) must not be what another finds in sys.modules
@@ -874,4 +1012,4 @@ if __name__ == "__main__":
     for w in which:
         {"voxelizer": gen_voxelizer, "configs": gen_configs, "dense": gen_dense_nets, "predict": gen_predict,
          "iou": gen_iou, "backbone": gen_backbone, "sweeps": gen_sweeps, "pillars": gen_pillars, "forecast": gen_forecast,
-         "forecast2": gen_forecast2, "forecast_edges": gen_forecast_edges}[w]()
+         "forecast2": gen_forecast2, "forecast_edges": gen_forecast_edges, "iou_edges": gen_iou_edges}[w]()
