@@ -27,7 +27,7 @@ def install_det3d_alias(force=False):
         return False
     if existing is not None and getattr(existing, "__futuredet_amd_alias__", False):
         return True
-    from . import apis, collate, config, config_tool, detectors, dist_infer, nms, registry, voxelize
+    from . import apis, collate, config, config_tool, detectors, dist_infer, nms, registry, solver, voxelize
     from . import backbones, heads, necks, readers  # noqa: F401  (populate the registries)
 
     _mod("det3d")
@@ -46,6 +46,10 @@ def install_det3d_alias(force=False):
          get_root_logger=apis.get_root_logger, set_random_seed=apis.set_random_seed, init_dist=apis.init_dist,
          build_optimizer=apis.build_optimizer, train_detector=apis.train_detector)
     _mod("det3d.torchie.apis.train", batch_processor=collate.batch_processor, example_to_device=collate.example_to_device)
+    # the training recipe (futuredet_amd.solver): a det3d training script builds OptimWrapper.create(...) and OneCycle(...) from here
+    _mod("det3d.solver")
+    _mod("det3d.solver.fastai_optim", OptimWrapper=solver.FusedAdam)
+    _mod("det3d.solver.learning_schedules_fastai", OneCycle=solver.OneCycle, LRSchedulerStep=solver.LRSchedulerStep)
     _mod("det3d.torchie.parallel")
     _mod("det3d.torchie.parallel.collate", collate_kitti_multi=collate.collate_kitti_multi, collate_kitti=collate.collate_kitti_multi)
     names = ("READERS", "BACKBONES", "NECKS", "HEADS", "LOSSES", "DETECTORS", "SECOND_STAGE", "ROI_HEAD")

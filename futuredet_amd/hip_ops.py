@@ -1115,3 +1115,101 @@ def forecast_from_detections(packed, counts, time, records=None, reject_thresh=2
     check(L.fd_forecast_from_detections(_p(packed), _p(counts), B, T, post, F, _p(records), _p(time), float(reject_thresh), float(match_thresh),
                                         ctypes.byref(out.c_struct), _stream()), "fd_forecast_from_detections")
     return out
+
+
+# ---- training: the fused optimiser step (fd_optim.hip) ----------------------------------------------------------------------------
+OPTIM_DECAY, OPTIM_HAS_GRAD = 1, 2  # FD_OPTIM_DECAY / FD_OPTIM_HAS_GRAD
+
+
+def optim_chunk():
+    return int(_lib.load().fd_optim_chunk())
+
+
+def optim_layout(numels, chunk):
+    """Host side of fd_optim_table for tensors of ``numels`` elements: (offsets int64 [n] -- each segment starts on a 16-byte boundary --,
+    total floats of a flat buffer, chunks int32 [n_chunks, 2] of (tensor, index of the chunk inside the tensor))."""
+    offsets, chunks, total = [], [], 0
+    for t, n in enumerate(numels):
+        n = int(n)
+        if n <= 0:
+            raise ValueError("tensor %d of the optimiser table is empty" % t)
+        offsets.append(total)
+        total += (n + 3) // 4 * 4
+        chunks += [(t, k) for k in range((n + chunk - 1) // chunk)]
+    return np.asarray(offsets, dtype=np.int64), total, np.asarray(chunks, dtype=np.int32).reshape(-1, 2)
+
+
+class AdamTable(object):
+    """The device-side description of a parameter set (struct fd_optim_table) with its flat gradient / exp_avg / exp_avg_sq buffers and
+    per-tensor step counts.  Built once; ``sync_pointers`` re-uploads the pointer table only when a parameter's storage has moved and
+    ``set_has_grad`` the flags only when the set of tensors with a gradient has changed -- both with non-blocking copies from fresh
+    pinned memory, so a step never waits for the device."""
+
+    def __init__(self, params, decay):
+        params = list(params)
+        if not params:
+            raise ValueError("the optimiser got no parameters")
+        for i, p in enumerate(params):
+            _dev(p, "parameter %d" % i, torch.float32)
+            if p.device != params[0].device:
+                raise FutureDetHipError("parameter %d lives on %s, the others on %s" % (i, p.device, params[0].device))
+        self.params, self.device = params, params[0].device
+        self.chunk = optim_chunk()
+        self.numel = [p.numel() for p in params]
+        offsets, self.total, chunks = optim_layout(self.numel, self.chunk)
+        self.offsets = [int(o) for o in offsets]
+        n, dev = len(params), self.device
+        self.grad, self.exp_avg, self.exp_avg_sq = (torch.zeros(self.total, dtype=torch.float32, device=dev) for _ in range(3))
+        self.step = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._coef = torch.zeros(2 * n, dtype=torch.float32, device=dev)
+        self._partials = torch.zeros(len(chunks), dtype=torch.float64, device=dev)
+        self.norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._numel_dev = torch.tensor(self.numel, dtype=torch.int64, device=dev)
+        self._offset_dev = torch.from_numpy(offsets).to(dev)
+        self._chunks_dev = torch.from_numpy(chunks).to(dev)
+        self._ptrs_dev = torch.zeros(n, dtype=torch.int64, device=dev)
+        self._flags_dev = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.decay = [bool(d) for d in decay]
+        assert len(self.decay) == n
+        self._ptrs, self._has_grad = None, None
+        self.sync_pointers()
+        self.set_has_grad([True] * n)
+        self.c_struct = _lib.OptimTable(
+            params=self._ptrs_dev.data_ptr(), numel=self._numel_dev.data_ptr(), offset=self._offset_dev.data_ptr(), flags=self._flags_dev.data_ptr(),
+            step=self.step.data_ptr(), coef=self._coef.data_ptr(), chunks=self._chunks_dev.data_ptr(), partials=self._partials.data_ptr(),
+            norm=self.norm.data_ptr(), grad=self.grad.data_ptr(), exp_avg=self.exp_avg.data_ptr(), exp_avg_sq=self.exp_avg_sq.data_ptr(),
+            total=self.total, n_tensors=n, n_chunks=len(chunks), chunk=self.chunk)
+
+    @staticmethod
+    def _upload(dst, values, np_dtype):
+        dst.copy_(torch.from_numpy(np.asarray(values, dtype=np_dtype)).pin_memory(), non_blocking=True)
+
+    def segment(self, flat, i):
+        """tensor i's view of one of the flat buffers, shaped like the parameter"""
+        return flat[self.offsets[i]:self.offsets[i] + self.numel[i]].view(self.params[i].shape)
+
+    def sync_pointers(self):
+        ptrs = [p.data_ptr() for p in self.params]
+        if ptrs != self._ptrs:
+            for i, p in enumerate(self.params):
+                if not p.is_contiguous() or p.numel() != self.numel[i]:
+                    raise FutureDetHipError("parameter %d changed its shape or is no longer contiguous" % i)
+            self._upload(self._ptrs_dev, ptrs, np.int64)  # device addresses lie below 2^63
+            self._ptrs = ptrs
+
+    def set_has_grad(self, has_grad):
+        if has_grad != self._has_grad:
+            self._upload(self._flags_dev, [(OPTIM_DECAY if d else 0) | (OPTIM_HAS_GRAD if h else 0) for d, h in zip(self.decay, has_grad)], np.int32)
+            self._has_grad = list(has_grad)
+
+
+def optim_zero_grad(table):
+    """fd_optim_zero_grad: zeroes the flat gradient buffer of an AdamTable (one launch)."""
+    check(_lib.load().fd_optim_zero_grad(ctypes.byref(table.c_struct), _stream()), "fd_optim_zero_grad")
+
+
+def optim_adam_step(table, lr, beta1, beta2, eps, wd, max_norm=0.0):
+    """fd_optim_adam_step on an AdamTable: decay, gradient clipping (max_norm > 0; total_norm and the coefficient land in table.norm) and
+    Adam for every tensor, in at most three launches.  No allocation, no synchronisation."""
+    check(_lib.load().fd_optim_adam_step(ctypes.byref(table.c_struct), float(lr), float(beta1), float(beta2), float(eps), float(wd), float(max_norm),
+                                         _stream()), "fd_optim_adam_step")

@@ -50,6 +50,12 @@ class TargetsCfg(ctypes.Structure):  # struct fd_targets_cfg
                 ("voxel_y", c_float), ("pc_x", c_float), ("pc_y", c_float), ("gaussian_overlap", ctypes.c_double)]
 
 
+class OptimTable(ctypes.Structure):  # struct fd_optim_table
+    _fields_ = [(n, c_void_p) for n in ("params", "numel", "offset", "flags", "step", "coef", "chunks", "partials", "norm", "grad", "exp_avg",
+                                        "exp_avg_sq")] + [("total", c_i64), ("n_tensors", ctypes.c_int32), ("n_chunks", ctypes.c_int32),
+                                                          ("chunk", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -152,6 +158,9 @@ SIGNATURES = {
     "fd_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "fd_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(TargetsCfg), c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_optim_chunk": (c_int, []),
+    "fd_optim_zero_grad": (c_int, [ctypes.POINTER(OptimTable), c_void_p]),
+    "fd_optim_adam_step": (c_int, [ctypes.POINTER(OptimTable)] + [ctypes.c_double] * 6 + [c_void_p]),
 }
 
 

@@ -568,6 +568,58 @@ int fd_pillar_train_backward(const float *voxels, const int32_t *num_points, con
                              const float *dout, float *dw1, float *dgamma1, float *dbeta1, float *dw2, float *dgamma2, float *dbeta2,
                              void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: one optimiser step for a whole model (fd_optim.hip).  Purely additive: fd_abi_version() stays 8.  fp32.
+ * Replaces, for the recipe of every shipped config (adam, fixed_wd, one_cycle, grad_clip max_norm / norm_type 2):
+ *   the true weight decay of OptimWrapper.step, p.data.mul_(1 - wd * lr) on every parameter of both groups
+ *     (det3d/solver/fastai_optim.py:158-174),
+ *   clip_grad_norm_ of OptimizerHook.after_train_iter (det3d/torchie/trainer/hooks/optimizer.py:9-19),
+ *   torch.optim.Adam(betas=(0.9, 0.99)).step() below it (det3d/torchie/apis/train.py:183-200), with the beta1 that OneCycle set for
+ *     this iteration (det3d/solver/learning_schedules_fastai.py:53-67),
+ *   and optimizer.zero_grad() (det3d/torchie/trainer/trainer.py:436-460 gives the order).
+ * The parameter set is described once, on the device.  Tensor t (n_tensors of them):
+ *   params[t]  uint64: address of the parameter's first element (contiguous fp32; any 4-byte alignment -- a tensor whose address is
+ *              not 16-byte aligned or whose numel is not a multiple of 4 takes a scalar path on the parameter side);
+ *   numel[t], offset[t]  int64: its length and where its segment starts in the three flat buffers grad / exp_avg / exp_avg_sq
+ *              (`total` floats each, 16-byte aligned; every offset a multiple of 4; the padding between segments stays zero);
+ *   flags[t]   int32: FD_OPTIM_DECAY (weight decay applies) | FD_OPTIM_HAS_GRAD (the tensor has a gradient this step);
+ *   step[t]    int32: the tensor's own Adam step count, advanced by the call for tensors with a gradient;
+ *   coef[2t..] fp32 scratch: lr / (1 - beta1^step), sqrt(1 - beta2^step), written by the call.
+ * Work is cut into chunks of at most `chunk` (= fd_optim_chunk() = FD_OPTIM_CHUNK) elements of ONE tensor: chunks[2c] = tensor,
+ * chunks[2c + 1] = index of the chunk inside the tensor (elements [index * chunk, ...)), n_chunks of them covering every tensor.
+ * partials: double[n_chunks] scratch;  norm: fp32[2], written by a clipping call: total_norm, min(1, max_norm / (total_norm + 1e-6)).
+ *
+ * fd_optim_adam_step, per element of a tensor with a gradient g (clipped on the fly, g <- g * norm[1]; grad is NOT rewritten):
+ *   p *= 1 - wd * lr (FD_OPTIM_DECAY);  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * in fp32 without contraction, the scalars rounded from double as torch rounds its python floats.  A tensor without a gradient is
+ * decayed only: moments and step stay.  max_norm > 0: three launches (per-chunk sums of squares of the gradients in double, a
+ * fixed-order finish in double, the step); max_norm <= 0: no clipping, two launches.  No atomics: the same bits on every run.
+ * fd_optim_zero_grad: zeroes the flat gradient buffer (one launch).
+ * Both validate on the host before any device work: a null table / member, n_tensors, n_chunks or total <= 0, chunk != FD_OPTIM_CHUNK,
+ * beta outside [0, 1), eps <= 0 are FD_EINVAL.  No allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_OPTIM_CHUNK 4096
+#define FD_OPTIM_DECAY 1
+#define FD_OPTIM_HAS_GRAD 2
+typedef struct fd_optim_table {
+    const void *params;
+    const void *numel, *offset;
+    const void *flags;
+    void *step;
+    void *coef;
+    const void *chunks;
+    void *partials;
+    void *norm;
+    float *grad, *exp_avg, *exp_avg_sq;
+    int64_t total;
+    int32_t n_tensors, n_chunks, chunk;
+} fd_optim_table;
+int fd_optim_chunk(void);
+int fd_optim_zero_grad(const fd_optim_table *table, fd_stream_t stream);
+int fd_optim_adam_step(const fd_optim_table *table, double lr, double beta1, double beta2, double eps, double wd, double max_norm,
+                       fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
