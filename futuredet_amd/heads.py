@@ -12,7 +12,8 @@ each task a DCNSepHead -- two deformable FeatureAdaption modules, a cls_head for
 launch of fd_deform_adapt_nhwc) with every mode whose reference forward runs (not forecast_feature / wide_head, 64 shared channels);
 ``two_stage`` is False in every shipped config and raises.  In eval mode on the device the head runs on the convolution plan of dense_bf16.py
 (the only device path; a head it cannot take raises); predict() runs the HIP decode + rotated NMS (fd_centerpoint_decode) for
-all (sample, heat-map) groups in one call.  loss() (training, torch ops) covers the standard and dense heads.
+all (sample, heat-map) groups in one call.  loss() (training, torch ops) covers the standard and dense heads; with ``fused_loss = True`` it runs
+on fd_loss.hip (two launches forward, two backward, no host synchronisation).
 """
 import copy
 import logging
@@ -189,6 +190,48 @@ class DCNSepHead(nn.Module):
         return self.forward_modules(x)
 
 
+class _FusedLossFunction(torch.autograd.Function):
+    """CenterHead.loss on fd_loss.hip: (holder, cfg, per-task targets, per-task map names, *maps) -> one 0-dim loss per task, each a view
+    of the terms vector that the call leaves in ``holder``.  The maps are flat: per task its ``hm`` followed by the maps of ``names``."""
+
+    @staticmethod
+    def forward(ctx, holder, cfg, targets, names, *maps):
+        maps = [m.contiguous() for m in maps]
+        ctx.cfg, ctx.targets, ctx.names = cfg, targets, names
+        tasks = _FusedLossFunction._tasks(targets, names, maps)
+        terms, sigs = hip_ops.centerhead_loss_forward(cfg, tasks)
+        holder["terms"], holder["sig"] = terms, sigs
+        ctx.terms = terms
+        ctx.save_for_backward(*maps)
+        stride = hip_ops.loss_terms_layout(cfg)[0]
+        return tuple(terms[k * stride] for k in range(len(targets)))
+
+    @staticmethod
+    def _tasks(targets, names, maps):
+        tasks, at = [], 0
+        for tg, nm in zip(targets, names):
+            tasks.append(dict(tg, hm=maps[at], maps=dict(zip(nm, maps[at + 1:at + 1 + len(nm)]))))
+            at += 1 + len(nm)
+        return tasks
+
+    @staticmethod
+    @once_differentiable  # the kernels are not differentiable themselves: a double backward raises here
+    def backward(ctx, *gos):
+        maps = ctx.saved_tensors
+        tasks = _FusedLossFunction._tasks(ctx.targets, ctx.names, maps)
+        flags = ctx.needs_input_grad[4:]
+        need, at = [], 0
+        for nm in ctx.names:
+            need.append({n for n, f in zip(["hm"] + list(nm), flags[at:at + 1 + len(nm)]) if f})
+            at += 1 + len(nm)
+        go = torch.stack([g.to(torch.float32) for g in gos])  # on the device: the upstream gradients are never read on the host
+        grads = hip_ops.centerhead_loss_backward(ctx.cfg, tasks, ctx.terms, go, need=need)
+        out = []
+        for g, nm in zip(grads, ctx.names):
+            out += [g.get(n) for n in ["hm"] + list(nm)]
+        return (None, None, None, None) + tuple(out)
+
+
 def _drop_caches(module, incompatible_keys=None):
     module._plan = None
     module.__dict__.pop("_wv_tensors", None)
@@ -267,6 +310,7 @@ class CenterHead(nn.Module):
             self.tasks.append(SepHead(cin, heads, bn=True, init_bias=init_bias, final_kernel=3, two_stage=self.two_stage,
                                       forecast_feature=self.forecast_feature, wide_head=self.wide_head))
         self.compute_dtype = torch.float32
+        self.fused_loss = False  # True: loss() of a standard / dense head runs on fd_loss.hip for fp32 maps on the device
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
         self.logger.info("Finish CenterHead Initialization")
@@ -313,12 +357,17 @@ class CenterHead(nn.Module):
         """center_head.py:396-539 for the standard (n0 / n3 / pedestrian) and dense (n3dtf / n3dtfm) heads.  ``example`` carries the
         reference pipeline's targets (hm / ind / mask / cat / anno_box, indexed [timestep][task]).  Returns the reference's dict of
         per-task lists (loss, hm_loss, loc_loss, loc_loss_elem, num_positive); like the reference it replaces preds_dict["hm"] by the
-        clamped sigmoid and adds preds_dict["anno_box"]."""
+        clamped sigmoid and adds preds_dict["anno_box"].
+
+        ``self.fused_loss = True`` (default False) sends fp32 maps on the device through fd_loss.hip instead (_loss_fused): the same
+        dict, with the intended differences listed there.  ``check=True`` then reads the kernels' status word back."""
         for flag in ("reverse", "sparse", "classify", "wide_head"):
             if getattr(self, flag):
                 raise NotImplementedError("CenterHead.loss: the %s head's loss is not implemented (standard and dense heads only)" % flag)
         if self.dataset not in ("waymo", "nuscenes"):
             raise NotImplementedError("CenterHead.loss: dataset %r (the reference handles waymo / nuscenes only)" % (self.dataset,))
+        if self.fused_loss and preds_dicts and all(p["hm"].is_cuda and p["hm"].dtype == torch.float32 for p in preds_dicts):
+            return self._loss_fused(example, preds_dicts, check=kwargs.get("check", False))
         T = self.timesteps
         rets = []
         for task_id, preds_dict in enumerate(preds_dicts):
@@ -370,6 +419,67 @@ class CenterHead(nn.Module):
         for ret in rets:
             for k, v in ret.items():
                 merged[k].append(v)
+        return merged
+
+    def _loss_fused(self, example, preds_dicts, check=False):
+        """loss() on fd_loss.hip (fd_centerhead_loss_forward / _backward): two launches forward and two backward for all tasks and
+        timesteps (three each for more than 8 tasks), no atomics, no host synchronisation, so a training step can be captured in a
+        graph.  Returns the reference's dict -- the same five keys and list lengths -- with every entry a view of ONE fp32 terms
+        vector on the device; only ``loss[k]`` carries a gradient.  Intended differences from the torch path:
+          * nothing is copied to the host: hm_loss, loc_loss_elem and num_positive stay device tensors (the torch path, like the
+            reference, moves them with .cpu(), a synchronisation per task);
+          * preds_dict["hm"] becomes the kernel's clamped sigmoid, a plain tensor without a gradient history;
+          * preds_dict["anno_box"] is not built.
+        An entry with mask != 0 whose ind / cat is out of range is skipped and counted (torch's gather would device-assert);
+        ``check=True`` reads that count back (a synchronisation) and raises AssertionError when it is not 0."""
+        T, dense = self.timesteps, bool(self.dense)
+        p0 = preds_dicts[0]
+        if "vel" in p0 and "rvel" in p0 and "rot" in p0 and "rrot" in p0:
+            names = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")
+        elif "vel" in p0 and "rot" in p0:
+            names = ("reg", "height", "dim", "vel", "rot")
+        else:
+            names = ("reg", "height", "dim", "rot")
+        D = {7: 14, 5: 10, 4: 8}[len(names)]
+        targets = []
+        for k in range(len(preds_dicts)):
+            if dense:
+                targets.append(dict(hm_target=example["hm"][k][0], ind=example["ind"][k][0], cat=example["cat"][k][0],
+                                    mask=[example["mask"][k][0]], anno_box=[example["anno_box"][k][0]]))
+            else:
+                targets.append(dict(hm_target=example["hm"][0][k], ind=example["ind"][0][k], cat=example["cat"][0][k],
+                                    mask=[example["mask"][i][k] for i in range(T)], anno_box=[example["anno_box"][i][k] for i in range(T)]))
+        B, _, H, W = p0["hm"].shape
+        M, row = targets[0]["anno_box"][0].shape[1:]
+        key = (B, H, W, M, len(preds_dicts), row, D, T, dense, tuple(self.code_weights), self.weight)
+        cached = self.__dict__.get("_loss_cfg")
+        if cached is None or cached[0] != key:  # the descriptor of the head mode and batch shape, built once
+            cwf = getattr(self, "code_weights_forecast", None) if (not dense and T > 1) else None
+            if not dense and T > 1 and cwf is None:
+                raise ValueError("CenterHead.loss: a standard head with %d timesteps needs code_weights_forecast (vel and rot heads)" % T)
+            cached = (key, hip_ops.make_loss_cfg(B, H, W, M, len(preds_dicts), dense, T, D, row, self.code_weights, cwf, self.weight))
+            self.__dict__["_loss_cfg"] = cached
+        cfg = cached[1]
+        holder = {}
+        maps = [p[n] for p in preds_dicts for n in ("hm",) + names]
+        losses = _FusedLossFunction.apply(holder, cfg, targets, [names] * len(preds_dicts), *maps)
+        terms = holder["terms"]
+        for p, sig in zip(preds_dicts, holder["sig"]):
+            p["hm"] = sig
+        if check:
+            bad = hip_ops.loss_status(terms)
+            if bad:
+                raise AssertionError("CenterHead.loss: %d masked target entries name a cell or class outside the heat map" % bad)
+        stride, S = hip_ops.loss_terms_layout(cfg)
+        merged = defaultdict(list)
+        for k in range(len(preds_dicts)):
+            t = terms[k * stride:(k + 1) * stride]
+            merged["loss"].append(losses[k])
+            merged["hm_loss"].append(t[1])
+            merged["loc_loss"].append([t[4 + i] for i in range(S)])
+            elem = t[4 + S:].view(S, D)
+            merged["loc_loss_elem"].append(elem[0] if dense else [elem[i] for i in range(S)])
+            merged["num_positive"].append(t[3])
         return merged
 
     # ----------------------------------------------------------------------------------------------- predict

@@ -1213,3 +1213,138 @@ def optim_adam_step(table, lr, beta1, beta2, eps, wd, max_norm=0.0):
     Adam for every tensor, in at most three launches.  No allocation, no synchronisation."""
     check(_lib.load().fd_optim_adam_step(ctypes.byref(table.c_struct), float(lr), float(beta1), float(beta2), float(eps), float(wd), float(max_norm),
                                          _stream()), "fd_optim_adam_step")
+
+
+# ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------
+LOSS_MAPS = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")  # fd_loss_task.maps / d_maps, in this order
+
+
+def loss_chunk():
+    """Heat-map elements per workgroup of the loss kernels (fd_loss_chunk())."""
+    return int(_lib.load().fd_loss_chunk())
+
+
+def loss_columns(D, row_stride):
+    """Target-row column of every predicted channel, the three branches of CenterHead.loss: 14 channels read the row as it is,
+    10 read [0..7, -2, -1] and 8 (no velocity) read [0..5, -2, -1]."""
+    if D == 14:
+        return list(range(14))
+    if D == 10:
+        return list(range(8)) + [row_stride - 2, row_stride - 1]
+    if D == 8:
+        return list(range(6)) + [row_stride - 2, row_stride - 1]
+    raise ValueError("CenterHead loss: 8, 10 or 14 box channels (got %d)" % D)
+
+
+def make_loss_cfg(B, H, W, M, n_tasks, dense, T, D, row_stride, code_weights, code_weights_forecast=None, weight=0.25):
+    """lib.LossCfg (struct fd_loss_cfg) of one head mode and batch shape; the code weights are python floats and stay doubles."""
+    c = _lib.LossCfg()
+    c.B, c.H, c.W, c.M, c.n_tasks, c.dense, c.T, c.D, c.row_stride = int(B), int(H), int(W), int(M), int(n_tasks), int(bool(dense)), int(T), int(D), int(row_stride)
+    if D in (8, 10, 14):
+        if len(code_weights) != D or (code_weights_forecast is not None and len(code_weights_forecast) != D):
+            raise ValueError("CenterHead loss: %d code weights for %d box channels" % (len(code_weights), D))
+        for i, col in enumerate(loss_columns(D, row_stride)):
+            c.col[i] = col
+        for i in range(D):
+            c.code_weights[i] = float(code_weights[i])
+            c.code_weights_forecast[i] = float(code_weights_forecast[i]) if code_weights_forecast is not None else 0.0
+    c.weight = float(weight)
+    return c
+
+
+def loss_terms_layout(cfg):
+    """(floats per task, terms per task S) of the terms vector: loss, hm_loss, num_pos, num_positive, loc_loss[S], loc_loss_elem[S][D]
+    per task, then one status word."""
+    S = 1 if cfg.dense else cfg.T
+    return 4 + S + S * cfg.D, S
+
+
+def _loss_tasks(cfg, tasks, sigs=None, grads=None):
+    """The fd_loss_task array of a call.  ``tasks``: per task a dict hm / hm_target / ind / cat, mask and anno_box (lists over the
+    task's terms; a standard head's mask list has every step's mask) and maps (name -> tensor).  Returns (array, largest C, keep-alive)."""
+    S = 1 if cfg.dense else cfg.T
+    arr = (_lib.LossTask * len(tasks))()
+    keep, cmax = [], 0
+    for k, t in enumerate(tasks):
+        hm = _dev(t["hm"], "hm", torch.float32)
+        B, C, H, W = hm.shape
+        if (B, H, W) != (cfg.B, cfg.H, cfg.W):
+            raise FutureDetHipError("CenterHead loss: heat map %s of task %d does not match B, H, W = %d, %d, %d" % (tuple(hm.shape), k, cfg.B, cfg.H, cfg.W))
+        cmax = max(cmax, C)
+        d = arr[k]
+        d.C = C
+        d.hm = hm.data_ptr()
+        tg = _dev(t["hm_target"], "hm_target", torch.float32)
+        assert tuple(tg.shape) == tuple(hm.shape), (tuple(tg.shape), tuple(hm.shape))
+        d.hm_target = tg.data_ptr()
+        ind, cat = _dev(t["ind"], "ind", torch.int64), _dev(t["cat"], "cat", torch.int64)
+        assert tuple(ind.shape) == tuple(cat.shape) == (cfg.B, cfg.M), (tuple(ind.shape), tuple(cat.shape))
+        d.ind, d.cat = ind.data_ptr(), cat.data_ptr()
+        assert len(t["mask"]) >= S and len(t["anno_box"]) >= S, "a mask and an anno_box per regression term"
+        for i in range(S):
+            mk = t["mask"][i]
+            if mk.dtype == torch.bool:
+                mk = mk.view(torch.uint8)
+            elif mk.dtype != torch.uint8:
+                mk = mk.ne(0).to(torch.uint8)
+            mk, an = _dev(mk, "mask", torch.uint8), _dev(t["anno_box"][i], "anno_box", torch.float32)
+            assert tuple(mk.shape) == (cfg.B, cfg.M) and tuple(an.shape) == (cfg.B, cfg.M, cfg.row_stride), (tuple(mk.shape), tuple(an.shape))
+            d.mask[i], d.anno_box[i] = mk.data_ptr(), an.data_ptr()
+            keep += [mk, an]
+        for i, name in enumerate(LOSS_MAPS):
+            m = t["maps"].get(name)
+            if m is None:
+                continue
+            m = _dev(m, name, torch.float32)
+            assert m.dim() == 4 and (m.shape[0], m.shape[2], m.shape[3]) == (B, H, W), (name, tuple(m.shape))
+            want = {"reg": 2, "height": 1, "dim": 3, "rot": 2, "rrot": 2}.get(name, 2 if cfg.dense else 2 * cfg.T)
+            if m.shape[1] != want:
+                raise FutureDetHipError("CenterHead loss: map %s of task %d has %d channels, the head mode needs %d" % (name, k, m.shape[1], want))
+            d.maps[i] = m.data_ptr()
+            if grads is not None and grads[k].get(name) is not None:
+                d.d_maps[i] = grads[k][name].data_ptr()
+        if sigs is not None:
+            d.sig = sigs[k].data_ptr()
+        if grads is not None and grads[k].get("hm") is not None:
+            d.d_hm = grads[k]["hm"].data_ptr()
+        keep += [hm, tg, ind, cat]
+    return arr, cmax, keep
+
+
+def centerhead_loss_forward(cfg, tasks):
+    """fd_centerhead_loss_forward: -> (terms vector fp32 on the device, layout of loss_terms_layout; the clamped sigmoid of every task's
+    heat map).  Two launches (three for more than 8 tasks), nothing is synchronised."""
+    L = _lib.load()
+    sigs = [torch.empty_like(_dev(t["hm"], "hm", torch.float32)) for t in tasks]
+    arr, cmax, keep = _loss_tasks(cfg, tasks, sigs=sigs)
+    dev = sigs[0].device
+    n_terms = L.fd_centerhead_loss_terms(ctypes.byref(cfg))
+    terms = torch.empty((max(int(n_terms), 1),), dtype=torch.float32, device=dev)
+    ws = workspace.get("loss", L.fd_centerhead_loss_workspace_bytes(ctypes.byref(cfg), cmax), dev)
+    check(L.fd_centerhead_loss_forward(ctypes.byref(cfg), arr, _p(terms), _p(ws), ws.numel(), _stream()), "fd_centerhead_loss_forward")
+    return terms, sigs
+
+
+def centerhead_loss_backward(cfg, tasks, terms, go, need=None):
+    """fd_centerhead_loss_backward: the gradient of sum_k go[k] * loss[k] w.r.t. every map -> per task a dict hm / reg / ... of new
+    tensors, every element written by the call.  ``go``: fp32 [n_tasks] on the device.  ``need``: per task a set of map names to
+    compute (default: all the task has)."""
+    L = _lib.load()
+    grads = []
+    for k, t in enumerate(tasks):
+        names = ["hm"] + [n for n in LOSS_MAPS if t["maps"].get(n) is not None]
+        grads.append({n: torch.empty_like(t["hm"] if n == "hm" else t["maps"][n]) for n in names if need is None or n in need[k]})
+    arr, cmax, keep = _loss_tasks(cfg, tasks, grads=grads)
+    dev = terms.device
+    go = _dev(go, "go", torch.float32)
+    assert go.numel() == len(tasks), (go.shape, len(tasks))
+    ws = workspace.get("loss", L.fd_centerhead_loss_workspace_bytes(ctypes.byref(cfg), cmax), dev)
+    check(L.fd_centerhead_loss_backward(ctypes.byref(cfg), arr, _p(_dev(terms, "terms", torch.float32)), _p(go), _p(ws), ws.numel(), _stream()),
+          "fd_centerhead_loss_backward")
+    return grads
+
+
+def loss_status(terms):
+    """The status word of a terms vector: the number of masked entries whose ind / cat were out of range (reads it back: a
+    synchronisation).  torch's gather would have device-asserted on them."""
+    return int(terms[-1].item())

@@ -56,6 +56,17 @@ class OptimTable(ctypes.Structure):  # struct fd_optim_table
                                                           ("chunk", ctypes.c_int32)]
 
 
+class LossCfg(ctypes.Structure):  # struct fd_loss_cfg
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "W", "M", "n_tasks", "dense", "T", "D", "row_stride")] + [
+        ("col", ctypes.c_int32 * 14), ("code_weights", ctypes.c_double * 14), ("code_weights_forecast", ctypes.c_double * 14),
+        ("weight", ctypes.c_double)]
+
+
+class LossTask(ctypes.Structure):  # struct fd_loss_task
+    _fields_ = [("hm", c_void_p), ("hm_target", c_void_p), ("ind", c_void_p), ("cat", c_void_p), ("mask", c_void_p * 7), ("maps", c_void_p * 7),
+                ("anno_box", c_void_p * 7), ("C", ctypes.c_int32), ("sig", c_void_p), ("d_hm", c_void_p), ("d_maps", c_void_p * 7)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -161,6 +172,11 @@ SIGNATURES = {
     "fd_optim_chunk": (c_int, []),
     "fd_optim_zero_grad": (c_int, [ctypes.POINTER(OptimTable), c_void_p]),
     "fd_optim_adam_step": (c_int, [ctypes.POINTER(OptimTable)] + [ctypes.c_double] * 6 + [c_void_p]),
+    "fd_loss_chunk": (c_int, []),
+    "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
+    "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),
+    "fd_centerhead_loss_forward": (c_int, [ctypes.POINTER(LossCfg), ctypes.POINTER(LossTask), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_centerhead_loss_backward": (c_int, [ctypes.POINTER(LossCfg), ctypes.POINTER(LossTask), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

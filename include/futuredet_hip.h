@@ -620,6 +620,84 @@ int fd_optim_zero_grad(const fd_optim_table *table, fd_stream_t stream);
 int fd_optim_adam_step(const fd_optim_table *table, double lr, double beta1, double beta2, double eps, double wd, double max_norm,
                        fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
+ * det3d/models/losses/centernet_loss.py as center_head.py:396-539 combines them, forward terms and the gradient of every head map.
+ * Purely additive: fd_abi_version() stays 8.  fp32 maps, contiguous [B, channels, H, W].
+ * Per task, x the raw heat map [B, C, H, W], sigma = sigmoid(x), s = clamp(sigma, 1e-4, 1 - 1e-4):
+ *   neg = sum log(1 - s) s^2 (1 - target)^4 over the map;  pos = sum_{b,m} log(s[b, cat, ind]) (1 - s[b, cat, ind])^2 mask[b, m];
+ *   num_pos = sum mask;  hm_loss = -(pos + neg) / num_pos, or -neg when num_pos == 0;
+ *   regression term i, predicted channel c:  elem[i][c] = sum_{b,m} mask |p_c[b, ind] - t_i[b, m, col[c]]| / (num_pos + 1e-4), the
+ *     divisor rounded to fp32 (RegLoss casts the mask to float, whatever the dtype of the maps);
+ *   loc_loss[i] = sum_c elem[i][c] cw_i[c];  loss = hm_loss + weight sum_i loc_loss[i].
+ * The predicted channels are reg(2), height(1), dim(3), vel(2)[, rvel(2)], rot(2)[, rrot(2)]: D = 8 (no vel), 10 or 14 of them;
+ * col[c] is the column of a target row (row_stride floats) that channel c is compared with.
+ *   standard head (dense = 0): one focal term on the targets of step 0 and T regression terms, all on ind / mask[0] of step 0; term i
+ *     reads anno_box[i] and velocity channels 2i, 2i + 1 (vel / rvel have 2T channels); cw_0 = code_weights, cw_{i>0} =
+ *     code_weights_forecast; num_positive = sum_i sum mask[i].  S = T terms.
+ *   dense head (dense = 1): task k is given the targets of its own step as mask[0] / anno_box[0]; one term with code_weights (vel /
+ *     rvel have 2 channels); num_positive = num_pos.  S = 1; T is ignored.
+ * mask holds 0 or 1 (any non-zero byte counts as 1).  An entry with mask == 0 contributes nothing and its ind / cat are never used;
+ * an entry with mask != 0 whose ind is outside [0, H W) or whose cat is outside [0, C) contributes nothing to pos / elem / the
+ * gradients and is counted in the status word (torch's gather would device-assert).  Objects that share a cell add their
+ * gradients in object order.
+ *
+ * fd_centerhead_loss_forward writes sig (the clamped sigmoid of every task's heat map) and the terms vector, fp32, per task
+ *   loss, hm_loss, num_pos, num_positive, loc_loss[S], loc_loss_elem[S][D]
+ * followed by ONE status word (the number of out-of-range entries over all tasks, as a float):
+ * fd_centerhead_loss_terms(cfg) = n_tasks (4 + S + S D) + 1 floats.
+ * fd_centerhead_loss_backward reads the same maps and targets, the terms vector of the forward call (num_pos) and go[n_tasks] (the
+ * upstream gradient of every task's loss, DEVICE memory) and writes d_hm / d_maps: every element exactly once, zeros where no
+ * object sits; a NULL output pointer skips that map.  Gradients of the clamped cells are exactly 0 (clamp's backward).
+ * Sums run in double in a fixed order (chunks of fd_loss_chunk() elements, samples in order, objects in order): no atomics, the same
+ * bits on every run.  Launches: 2 per call for up to 8 tasks, 3 for 9 to 16.  Descriptors travel as launch arguments: no
+ * allocation, no copy, no synchronisation; nothing is cached between calls.
+ * workspace >= fd_centerhead_loss_workspace_bytes(cfg, largest C of the tasks) (0 = invalid sizes), 16-byte aligned; the backward
+ * does not need the forward's contents.  Both entry points validate on the host before any device work; FD_EINVAL for: a null cfg /
+ * tasks / terms / go / workspace or a null member that the mode needs; B, H, W, M or a task's C <= 0; n_tasks outside [1, 16]; T
+ * outside [1, 7] (standard); D not 8, 10 or 14; M above FD_LOSS_MAX_OBJS; a column outside the target row; a map of 2^31 elements or
+ * more; a workspace that is too small.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_LOSS_CHUNK 2048
+#define FD_LOSS_MAX_TASKS 16
+#define FD_LOSS_MAX_STEPS 7
+#define FD_LOSS_MAX_OBJS 2048
+typedef struct fd_loss_cfg {
+    int32_t B;
+    int32_t H;
+    int32_t W;
+    int32_t M;
+    int32_t n_tasks;
+    int32_t dense;
+    int32_t T;
+    int32_t D;
+    int32_t row_stride;
+    int32_t col[14];
+    double code_weights[14];
+    double code_weights_forecast[14];
+    double weight;
+} fd_loss_cfg;
+typedef struct fd_loss_task {
+    const float *hm;        /* raw heat map [B, C, H, W] */
+    const float *hm_target; /* [B, C, H, W] */
+    const int64_t *ind;     /* [B, M] */
+    const int64_t *cat;     /* [B, M] */
+    const void *mask[7];    /* uint8 [B, M] per step (standard: T of them; dense: [0]) */
+    const float *maps[7];   /* reg, height, dim, vel, rvel, rot, rrot; NULL where D has no such channels */
+    const float *anno_box[7]; /* fp32 [B, M, row_stride] per term */
+    int32_t C;
+    float *sig;             /* forward: clamped sigmoid [B, C, H, W] */
+    float *d_hm;            /* backward outputs (NULL: skipped) */
+    float *d_maps[7];
+} fd_loss_task;
+int fd_loss_chunk(void);
+size_t fd_centerhead_loss_terms(const fd_loss_cfg *cfg);
+size_t fd_centerhead_loss_workspace_bytes(const fd_loss_cfg *cfg, int max_classes);
+int fd_centerhead_loss_forward(const fd_loss_cfg *cfg, const fd_loss_task *tasks, float *terms, void *workspace, size_t workspace_bytes,
+                               fd_stream_t stream);
+int fd_centerhead_loss_backward(const fd_loss_cfg *cfg, const fd_loss_task *tasks, const float *terms, const float *go, void *workspace,
+                                size_t workspace_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
