@@ -51,6 +51,15 @@ class SparseBasicBlock(spconv.SparseModule):
         out.features = self.relu(out.features + identity.features)
         return out
 
+    def forward_fused_bn(self, x, bn_act):
+        """forward with bn1 + relu and bn2 + identity + relu each handed to ``bn_act(features, bn, relu module, residual)``"""
+        out = self.conv1(x)
+        out.features = bn_act(out.features, self.bn1, self.relu)
+        out = self.conv2(out)
+        identity = x if self.downsample is None else self.downsample(x)
+        out.features = bn_act(out.features, self.bn2, self.relu, identity.features)
+        return out
+
 
 @BACKBONES.register_module
 class SpMiddleResNetFHD(nn.Module):
@@ -79,17 +88,52 @@ class SpMiddleResNetFHD(nn.Module):
         self.dense_channels_last = True
         self.dense_dtype = None              # dtype of the BEV map handed to the neck (default: compute dtype)
         self.profile_hook = None             # callable(tag, algorithmic_bytes, flops, fn) used by bench.py
+        self.fused_bn = False                # training: BatchNorm1d (+ residual) + ReLU on the fused kernels (sparse.batch_norm_act)
 
     # ------------------------------------------------------------------------------------------------ generic
+    def _bn_act(self, features, bn, relu, residual=None):
+        """relu(bn(features) [+ residual]): the fused kernels where they apply, else the modules as SparseSequential / SparseBasicBlock
+        call them (CPU, double, eval, no_grad, affine=False, track_running_stats=False, momentum=None, fewer than 2 rows)."""
+        if spconv.batch_norm_fusable(features, bn):
+            return spconv.batch_norm_act(features, bn, residual=residual, relu=True)
+        out = bn(features)
+        if residual is not None:
+            out = out + residual
+        return relu(out)
+
+    def _run_stage(self, seq, x):
+        """SparseSequential.forward with every BatchNorm1d + ReLU pair and every block's normalisation chain through _bn_act"""
+        mods = list(seq._modules.values())
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, SparseBasicBlock):
+                x = m.forward_fused_bn(x, self._bn_act)
+            elif isinstance(m, spconv.SparseModule):
+                x = m(x)
+            elif x.features.shape[0] != 0:
+                if isinstance(m, nn.BatchNorm1d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU):
+                    x.features = self._bn_act(x.features, m, mods[i + 1])
+                    i += 1
+                else:
+                    x.features = m(x.features)
+            i += 1
+        return x
+
     def forward_generic(self, voxel_features, coors, batch_size, input_shape):
         sparse_shape = np.array(input_shape[::-1]) + [1, 0, 0]  # scn.py:151
         ret = spconv.SparseConvTensor(voxel_features, coors.int(), sparse_shape, batch_size)
-        x = self.conv_input(ret)
-        x_conv1 = self.conv1(x)
-        x_conv2 = self.conv2(x_conv1)
-        x_conv3 = self.conv3(x_conv2)
-        x_conv4 = self.conv4(x_conv3)
-        ret = self.extra_conv(x_conv4).dense()
+        stages = (self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.extra_conv)
+        if self.fused_bn and self.training and torch.is_grad_enabled():
+            run = [lambda x, seq=seq: self._run_stage(seq, x) for seq in stages]
+        else:
+            run = stages
+        x = run[0](ret)
+        x_conv1 = run[1](x)
+        x_conv2 = run[2](x_conv1)
+        x_conv3 = run[3](x_conv2)
+        x_conv4 = run[4](x_conv3)
+        ret = run[5](x_conv4).dense()
         N, C, D, H, W = ret.shape
         ret = ret.view(N, C * D, H, W)
         return ret, {"conv1": x_conv1, "conv2": x_conv2, "conv3": x_conv3, "conv4": x_conv4}

@@ -1348,3 +1348,61 @@ def loss_status(terms):
     """The status word of a terms vector: the number of masked entries whose ind / cat were out of range (reads it back: a
     synchronisation).  torch's gather would have device-asserted on them."""
     return int(terms[-1].item())
+
+
+# ------------------------------------------------------------------------------------------------ sparse BatchNorm (training)
+def sparse_bn_chunk():
+    """Rows per chunk of the sparse BatchNorm's sums (FD_SPARSE_BN_CHUNK): part of the summation order."""
+    return int(_lib.load().fd_sparse_bn_chunk())
+
+
+def sparse_bn_channels_ok(c):
+    return c % 16 == 0 and 16 <= c <= 128
+
+
+def _sparse_bn_ws(L, n, c, device):
+    return workspace.get("sparse_bn", L.fd_sparse_bn_workspace_bytes(int(n), int(c)), device)
+
+
+def sparse_bn_train_forward(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, residual=None, relu=True,
+                            n_dev=None):
+    """fd_sparse_bn_train_forward: y = act(gamma (x - mean) invstd + beta [+ residual]) on batch statistics over the rows of x [n, C]
+    fp32; updates running_mean / running_var / num_batches_tracked in place on the device (their ``_version`` is NOT bumped: the
+    caller does that).  ``n_dev``: int32 [1] on the device, the valid row count (n = x.shape[0] is then the capacity).
+    Returns (y, saved [2, C] = mean, invstd).  Two launches, nothing is synchronised."""
+    L = _lib.load()
+    x = _dev(x, "x", torch.float32)
+    n, c = x.shape
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if _dev(t, name, torch.float32).numel() != c:
+            raise FutureDetHipError("%s must hold %d channels, got %d" % (name, c, t.numel()))
+    _dev(num_batches_tracked, "num_batches_tracked", torch.int64)
+    if residual is not None and _dev(residual, "residual", torch.float32).shape != x.shape:
+        raise FutureDetHipError("residual must be %s, got %s" % (tuple(x.shape), tuple(residual.shape)))
+    out = torch.empty_like(x)
+    saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = _sparse_bn_ws(L, n, c, x.device)
+    check(L.fd_sparse_bn_train_forward(_p(x), _p(residual), _p(gamma), _p(beta), n, _p(n_dev), c, int(bool(relu)), float(eps), float(momentum),
+                                       _p(out), _p(saved), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel(),
+                                       _stream()), "fd_sparse_bn_train_forward")
+    return out, saved
+
+
+def sparse_bn_train_backward(dy, x, y, gamma, saved, relu=True, want_residual=False, n_dev=None):
+    """fd_sparse_bn_train_backward: -> (dx, d_residual or None, dgamma, dbeta).  ``y`` is the forward's output (the ReLU mask; may be
+    None with relu=False), ``saved`` what the forward returned."""
+    L = _lib.load()
+    dy = _dev(dy, "dy", torch.float32)
+    x = _dev(x, "x", torch.float32)
+    n, c = x.shape
+    if dy.shape != x.shape or (y is not None and _dev(y, "y", torch.float32).shape != x.shape):
+        raise FutureDetHipError("dy and y must be %s" % (tuple(x.shape),))
+    if _dev(saved, "saved", torch.float32).numel() != 2 * c or _dev(gamma, "gamma", torch.float32).numel() != c:
+        raise FutureDetHipError("gamma / saved do not hold %d channels" % c)
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_residual else None
+    dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = _sparse_bn_ws(L, n, c, x.device)
+    check(L.fd_sparse_bn_train_backward(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), n, _p(n_dev), c, int(bool(relu)), _p(dx), _p(dres),
+                                        _p(dgb[0]), _p(dgb[1]), _p(ws), ws.numel(), _stream()), "fd_sparse_bn_train_backward")
+    return dx, dres, dgb[0], dgb[1]

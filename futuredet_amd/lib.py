@@ -177,6 +177,12 @@ SIGNATURES = {
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),
     "fd_centerhead_loss_forward": (c_int, [ctypes.POINTER(LossCfg), ctypes.POINTER(LossTask), c_void_p, c_void_p, c_size_t, c_void_p]),
     "fd_centerhead_loss_backward": (c_int, [ctypes.POINTER(LossCfg), ctypes.POINTER(LossTask), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_sparse_bn_chunk": (c_int, []),
+    "fd_sparse_bn_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "fd_sparse_bn_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int, c_float, ctypes.c_double,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_sparse_bn_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -152,6 +152,53 @@ class _SparseConvFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+class _SparseBatchNormFunction(torch.autograd.Function):
+    """Training-mode BatchNorm1d over the rows of x [n, C] fused with the residual add and ReLU that follow it (fd_sparse_bn.hip):
+    y = act(gamma (x - mean) invstd + beta [+ residual]).  ``bn`` is the nn.BatchNorm1d module: the kernel updates its running
+    statistics and num_batches_tracked on the device.  Saves x and y: y is what the next convolution saves as its input."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, residual, bn, relu):
+        y, saved = hip_ops.sparse_bn_train_forward(x, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps,
+                                                   bn.momentum, residual=residual, relu=relu)
+        # the kernel wrote through raw pointers: packed_weight keys the eval path's folded-BN cache on these counters
+        for buf in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+            torch.autograd.graph.increment_version(buf)
+        ctx.save_for_backward(x, y, gamma, saved)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, y, gamma, saved = ctx.saved_tensors
+        want_res = ctx.needs_input_grad[3]
+        dx, dres, dgamma, dbeta = hip_ops.sparse_bn_train_backward(dy.float().contiguous(), x, y, gamma, saved, relu=ctx.relu,
+                                                                   want_residual=want_res)
+        return dx, dgamma, dbeta, dres, None, None
+
+
+def batch_norm_fusable(features, bn):
+    """True where batch_norm_act can take the place of ``bn`` (+ residual add + ReLU): a training-mode, affine nn.BatchNorm1d that
+    tracks running statistics with a fixed momentum, gradients enabled, fp32 device features [n >= 2, C] with a supported C."""
+    return (isinstance(bn, nn.BatchNorm1d) and bn.training and torch.is_grad_enabled() and bn.affine and bn.track_running_stats
+            and bn.momentum is not None and bn.running_mean is not None and features.is_cuda and features.dtype == torch.float32
+            and bn.weight.dtype == torch.float32 and bn.weight.device == features.device and features.dim() == 2
+            and features.shape[0] >= 2 and hip_ops.sparse_bn_channels_ok(features.shape[1]))
+
+
+def batch_norm_act(features, bn, residual=None, relu=True):
+    """relu(bn(features) [+ residual]) in training mode on the fused kernels; ``bn`` is the existing nn.BatchNorm1d module (parameters,
+    buffers and state-dict keys unchanged).  Raises where batch_norm_fusable(features, bn) does not hold: there is no fallback here."""
+    if not batch_norm_fusable(features, bn):
+        raise hip_ops.FutureDetHipError("batch_norm_act: needs a training-mode affine BatchNorm1d with running statistics and a momentum, "
+                                        "gradients enabled and fp32 device features [n >= 2, C], C a multiple of 16 up to 128 (got %s %s)"
+                                        % (tuple(features.shape), features.dtype))
+    if residual is not None:
+        residual = residual.float().contiguous()
+    return _SparseBatchNormFunction.apply(features.contiguous(), bn.weight, bn.bias, residual, bn, bool(relu))
+
+
 class SparseConvolution(SparseModule):
     def __init__(self, ndim, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, subm=False, indice_key=None):

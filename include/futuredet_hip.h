@@ -698,6 +698,37 @@ int fd_centerhead_loss_forward(const fd_loss_cfg *cfg, const fd_loss_task *tasks
 int fd_centerhead_loss_backward(const fd_loss_cfg *cfg, const fd_loss_task *tasks, const float *terms, const float *go, void *workspace,
                                 size_t workspace_bytes, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: BatchNorm1d on batch statistics over the rows of a sparse feature matrix, fused with the ReLU and the residual add that
+ * follow it in SpMiddleResNetFHD (fd_sparse_bn.hip).  Purely additive: fd_abi_version() stays 8.
+ * fp32, row-major contiguous x [n, C]; C a multiple of 16 in [16, 128]; relu 0 or 1; residual [n, C] or NULL.
+ *   forward:  y = act(gamma (x - mean) invstd + beta [+ residual]);  mean and the biased variance over the valid rows,
+ *             invstd = 1 / sqrt(var + eps);  saved = [mean[C], invstd[C]] fp32 for the backward;
+ *             running_mean <- (1 - momentum) running_mean + momentum mean, running_var the same with the unbiased variance
+ *             var n / (n - 1), num_batches_tracked (int64) += 1 -- all on the device.
+ *   backward: g = dy where y > 0 (relu = 1; y is the forward's output) or dy;  dbeta = sum g;  dgamma = sum g x^,
+ *             x^ = (x - mean) invstd;  dx = gamma invstd (g - dbeta / n - x^ dgamma / n);  d_residual = g (NULL: skipped).
+ * Sums: rows are cut into chunks of fd_sparse_bn_chunk() (= FD_SPARSE_BN_CHUNK) rows; a chunk's partial is centred at the chunk's own
+ * mean; partials are combined in double, in a fixed order, with Chan's rule.  No atomics: the same bits on every run.
+ * n_dev (may be NULL): the valid row count in device memory; n is then the capacity, the statistics use min(n, max(*n_dev, 0)) rows, and
+ * the rows at or beyond it are written as zeros in y, dx and d_residual and never read.  A device count of 0 leaves the running
+ * statistics and num_batches_tracked as they are; a device count of 1 gives a variance of 0 (torch raises; a kernel cannot).
+ * Two launches per call; no allocation, no synchronisation.  workspace >= fd_sparse_bn_workspace_bytes(n, C) (0 = invalid sizes),
+ * 16-byte aligned like every tensor; the backward does not need the forward's contents.
+ * Both entry points validate on the host before any device work; FD_EINVAL for: a null pointer (other than residual, n_dev,
+ * d_residual, and y when relu = 0), an unsupported C, n outside [1, 2^30], n < 2 without n_dev, relu not 0 or 1, eps <= 0, momentum
+ * outside [0, 1], a misaligned tensor, a workspace that is too small.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_SPARSE_BN_CHUNK 256
+int fd_sparse_bn_chunk(void);
+size_t fd_sparse_bn_workspace_bytes(int64_t n, int C);
+int fd_sparse_bn_train_forward(const float *x, const float *residual, const float *gamma, const float *beta, int64_t n, const int32_t *n_dev,
+                               int C, int relu, float eps, double momentum, float *y, float *saved, float *running_mean, float *running_var,
+                               int64_t *num_batches_tracked, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_sparse_bn_train_backward(const float *dy, const float *x, const float *y, const float *gamma, const float *saved, int64_t n,
+                                const int32_t *n_dev, int C, int relu, float *dx, float *d_residual, float *dgamma, float *dbeta,
+                                void *workspace, size_t workspace_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
