@@ -11,31 +11,71 @@
 namespace fd {
 
 void set_error(const char *fmt, ...);
-int spconv_f32_compact_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr,
-                                int64_t nbr_stride, int K, int64_t n_in_bound, int n_out, const int *n_out_dev, int cin, int cout, float *out,
-                                const int *ranges, int n_ranges, hipStream_t stream);
 
-// fd_spconv_bf16win.hip: 64 -> 64, 128 -> 128 with an LDS window of input rows and 32-row MFMA tiles; its weight layout
-// follows the standard one in the packed buffer (spconv_bf16_win_weight_bytes > 0); 1 = launched, 0 = shape not covered
-size_t spconv_bf16_win_weight_bytes(int K, int cin, int cout);
+// ---- sparse convolution: one call record, one description of the packed-weight buffer ---------------------------
+// fd_spconv_apply validates its arguments, fills this record once and offers it to the kernel families in turn.
+struct SpconvCall {
+    const void *in;
+    int64_t n_in;         // rows of `in` (bound of the rulebook entries)
+    const void *wpacked;  // start of the whole packed buffer: a family finds its section through spconv_weight_layout
+    const float *bias;
+    const void *residual;
+    int relu;
+    const int *nbr;
+    int64_t nbr_stride;
+    const int *ranges;  // null: equal-row ranges
+    int n_ranges;
+    int K, n_out;
+    const int *n_out_dev;
+    int64_t n_expected;  // only steers launch heuristics
+    int cin, cout, dtype;
+    void *out;
+    hipStream_t stream;
+};
+
+// The buffer fd_spconv_pack_weight / fd_spconv_pack_weight_device write and the kernels read, as byte sections (bytes 0 = absent):
+//   base  [K][cin / 16 (bf16, cin >= 32: cin / 32)][cout / 16][64 lanes] fragments of the 16x16 MFMAs: every shape
+//   c32   fp32 32 -> 32: the 32x32x2 fragment order of fd_spconv_c32.hip
+//   pair  bf16 with 16 input channels: two taps stacked along K = 32 (fd_spconv_bf16.hip), ceil(K / 2) tap pairs
+//   win   bf16 64 -> 64 and 128 -> 128: the 32x32x16 fragment order of the LDS-window kernel (fd_spconv_bf16win.hip)
+struct WeightSection {
+    size_t offset, bytes;
+};
+struct SpconvWeightLayout {
+    WeightSection base, c32, pair, win;
+    size_t total;
+};
+inline SpconvWeightLayout spconv_weight_layout(int K, int cin, int cout, int dtype) {
+    const size_t elem = dtype == 0 ? 4 : 2, main_bytes = (size_t)K * cin * cout * elem;
+    SpconvWeightLayout l{};
+    size_t end = 0;
+    auto section = [&](bool present, size_t bytes) {
+        const WeightSection s{end, present ? bytes : 0};
+        end += s.bytes;
+        return s;
+    };
+    l.base = section(true, main_bytes);
+    l.c32 = section(dtype == 0 && cin == 32 && cout == 32, main_bytes);
+    l.pair = section(dtype == 1 && cin == 16, (size_t)((K + 1) / 2) * 32 * cout * elem);
+    l.win = section(dtype == 1 && ((cin == 64 && cout == 64) || (cin == 128 && cout == 128)), main_bytes);
+    l.total = end;
+    return l;
+}
+inline SpconvWeightLayout spconv_weight_layout(const SpconvCall &c) { return spconv_weight_layout(c.K, c.cin, c.cout, c.dtype); }
+
+// The kernel families of fd_spconv_apply, in the order it tries them: 1 = launched, 0 = not this family's shape.
+int spconv_f32_res16_dispatch(const SpconvCall &c);    // fd_spconv_f32r.hip: fp32, 16 input channels (weights resident in LDS, register accumulators)
+int spconv_f32_c32_dispatch(const SpconvCall &c);      // fd_spconv_c32.hip: fp32 32 -> 32 on the 32x32x2 MFMA
+int spconv_f32_compact_dispatch(const SpconvCall &c);  // fd_spconv_v2.hip: fp32, pair compaction
+int spconv_bf16_win_dispatch(const SpconvCall &c);     // fd_spconv_bf16win.hip: 64 -> 64, 128 -> 128 with an LDS window of input rows and 32-row MFMA tiles
+int spconv_bf16_ws_dispatch(const SpconvCall &c);      // fd_spconv_bf16.hip: RESIDENT / RING kernels
+// fd_spconv_bf16win.hip: writes the win section
 void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*tobf)(float), uint16_t *dst);
-int spconv_bf16_win_dispatch(const void *in, const void *wp_win, const float *bias, const void *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                             int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, void *out, hipStream_t stream);
-int spconv_bf16_ws_dispatch(const void *in, const void *wp, const float *bias, const void *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                            int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, void *out, hipStream_t stream);
 
 // fd_conv2d_wino_pc.hip: 0 = launched, 1 = shape not supported by the variant, -1 = dynamic LDS refused; wide_items: work items of 128
 // output channels (tile 8) instead of 64 (tile 7)
 int wino_pc_launch(const float *x, const void *wp, const float *bias, float *y, int B, int H, int W, int cin, int cout, int relu, int cout_total,
                    int co_off, int wide_items, hipStream_t stream);
-
-// fd_spconv_f32r.hip: fp32, 16 input channels (weights resident in LDS, register accumulators, empty items skipped); 1 = launched
-int spconv_f32_res16_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                              int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, float *out, hipStream_t stream);
-
-int spconv_f32_c32_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr,
-                            int64_t nbr_stride, int K, int64_t n_in_bound, int n_out, const int *n_out_dev, int cin, int cout, float *out,
-                            const int *ranges, int n_ranges, hipStream_t stream);
 
 // Element counts that only the device knows (voxels of a sweep, rows of a sparse level): entry points take the host-side
 // CAPACITY plus an optional device pointer to the actual count; kernels are launched for the capacity and work on
@@ -82,9 +122,17 @@ int device_cu_count();  // compute units of the current device, cached per devic
 // Kernels that need more than 64 KB of dynamic LDS must be told so once per (kernel, device).  `done` is the
 // kernel instantiation's own bit mask of devices already configured.  Returns false when the runtime refuses.
 bool ensure_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint64_t> &done);
-// Tuning / test knobs (fd_tuning_set; initial values are read ONCE from the FD_* environment variables when the
-// library is loaded).  0 = the built-in heuristic.
-enum TuneKey { kTuneSpconvRG = 0, kTuneSpconvV1, kTuneSpconvBf16V1, kTuneV2Depth, kTuneV2TM, kTuneV2LdsPad, kTuneConvNT, kTuneV2RangesPerCU, kTuneV2Uniform, kTuneV2RowCost, kTuneSpconvC32, kTuneBf16GP, kTuneBf16RG, kTuneBf16Depth, kTuneBf16NW, kTuneStrict, kTuneBf16Win, kTuneF32ResRG, kTuneConvStrip, kTuneF32ResNW, kTuneCount };
+// Tuning / test knobs (fd_tuning_set; initial values are read ONCE from the environment when the library is loaded: the
+// variable of a knob is FD_ + its upper-case name).  0 = the built-in heuristic.  This list is the only one: the enum, the
+// names fd_tuning_set accepts and the environment variables all come from it.
+#define FD_TUNE_KNOBS(X)                                                                                                       \
+    X(kTuneSpconvRG, "spconv_rg") X(kTuneSpconvV1, "spconv_v1") X(kTuneConvNT, "conv_nt") X(kTuneV2RangesPerCU, "v2_ranges_per_cu") \
+    X(kTuneSpconvC32, "spconv_c32") X(kTuneBf16GP, "bf16_gp") X(kTuneBf16RG, "bf16_rg") X(kTuneBf16Depth, "bf16_depth")        \
+    X(kTuneBf16NW, "bf16_nw") X(kTuneBf16Win, "bf16_win") X(kTuneF32ResRG, "f32_res_rg") X(kTuneConvStrip, "conv_strip")       \
+    X(kTuneF32ResNW, "f32_res_nw")
+#define FD_TUNE_ENUM(key, name) key,
+enum TuneKey { FD_TUNE_KNOBS(FD_TUNE_ENUM) kTuneCount };
+#undef FD_TUNE_ENUM
 int tuning(TuneKey key);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -1,5 +1,6 @@
 // Process-level pieces of the C ABI: thread-local last-error text (never exit()), per-device caches and the
 // tuning knobs.
+#include <ctype.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -53,13 +54,18 @@ bool ensure_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint64_t> 
 }
 
 namespace {
+#define FD_TUNE_NAME(key, name) name,
+const char *const kTuneNames[kTuneCount] = {FD_TUNE_KNOBS(FD_TUNE_NAME)};
+#undef FD_TUNE_NAME
 struct TuneTable {
     std::atomic<int> v[kTuneCount];
     TuneTable() {
-        static const char *const env[kTuneCount] = {"FD_SPCONV_RG", "FD_SPCONV_V1", "FD_SPCONV_BF16_V1", "FD_V2_DEPTH", "FD_V2_TM",
-                                                    "FD_V2_LDSPAD", "FD_CONV_NT", "FD_V2_RANGES_PER_CU", "FD_V2_UNIFORM", "FD_V2_ROWCOST", "FD_SPCONV_C32", "FD_BF16_GP", "FD_BF16_RG", "FD_BF16_DEPTH", "FD_BF16_NW", "FD_STRICT", "FD_BF16_WIN", "FD_F32_RES_RG", "FD_CONV_STRIP", "FD_F32_RES_NW"};
         for (int i = 0; i < kTuneCount; ++i) {
-            const char *e = getenv(env[i]);
+            char env[64] = "FD_";
+            size_t n = 3;
+            for (const char *c = kTuneNames[i]; *c && n + 1 < sizeof(env); ++c) env[n++] = (char)toupper((unsigned char)*c);
+            env[n] = 0;
+            const char *e = getenv(env);
             v[i].store(e ? atoi(e) : 0, std::memory_order_relaxed);
         }
     }
@@ -68,7 +74,6 @@ TuneTable &tune_table() {
     static TuneTable t;  // constructed once, thread-safe (C++11); the environment is read here and nowhere else
     return t;
 }
-const char *const kTuneNames[kTuneCount] = {"spconv_rg", "spconv_v1", "spconv_bf16_v1", "v2_depth", "v2_tm", "v2_ldspad", "conv_nt", "v2_ranges_per_cu", "v2_uniform", "v2_rowcost", "spconv_c32", "bf16_gp", "bf16_rg", "bf16_depth", "bf16_nw", "strict", "bf16_win", "f32_res_rg", "conv_strip", "f32_res_nw"};
 }  // namespace
 
 int tuning(TuneKey key) { return tune_table().v[key].load(std::memory_order_relaxed); }

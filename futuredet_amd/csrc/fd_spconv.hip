@@ -219,36 +219,24 @@ __global__ void __launch_bounds__(256) spconv_bf16(const unsigned short *__restr
     }
 }
 
-struct LaunchArgs {
-    const void *in, *wp;
-    const float *bias;
-    const void *residual;
-    int relu;
-    const int *nbr;
-    int64_t nbr_stride;
-    int K, n_out;
-    const int *n_out_dev;
-    void *out;
-    hipStream_t stream;
-};
-
 template <int CIN, int COUT, int RG>
-void launch(const LaunchArgs &a, int dtype) {
+void launch(const fd::SpconvCall &a) {
     const int rows_b = 64 * RG;
     dim3 grid((unsigned)((a.n_out + rows_b - 1) / rows_b));
-    if (dtype == 0)
-        hipLaunchKernelGGL((spconv_f32<CIN, COUT, RG>), grid, dim3(256), 0, a.stream, (const float *)a.in, (const float4 *)a.wp, a.bias,
+    const void *wp = (const char *)a.wpacked + fd::spconv_weight_layout(a).base.offset;
+    if (a.dtype == 0)
+        hipLaunchKernelGGL((spconv_f32<CIN, COUT, RG>), grid, dim3(256), 0, a.stream, (const float *)a.in, (const float4 *)wp, a.bias,
                            (const float *)a.residual, a.relu, a.nbr, a.nbr_stride, a.K, a.n_out, a.n_out_dev, (float *)a.out);
     else
-        hipLaunchKernelGGL((spconv_bf16<CIN, COUT, RG>), grid, dim3(256), 0, a.stream, (const unsigned short *)a.in, a.wp, a.bias,
+        hipLaunchKernelGGL((spconv_bf16<CIN, COUT, RG>), grid, dim3(256), 0, a.stream, (const unsigned short *)a.in, wp, a.bias,
                            (const unsigned short *)a.residual, a.relu, a.nbr, a.nbr_stride, a.K, a.n_out, a.n_out_dev, (unsigned short *)a.out);
 }
 
 template <int CIN, int COUT>
-void launch_rg(const LaunchArgs &a, int dtype, int rg) {
-    if (rg >= 4) launch<CIN, COUT, 4>(a, dtype);
-    else if (rg == 2) launch<CIN, COUT, 2>(a, dtype);
-    else launch<CIN, COUT, 1>(a, dtype);
+void launch_rg(const fd::SpconvCall &a, int rg) {
+    if (rg >= 4) launch<CIN, COUT, 4>(a);
+    else if (rg == 2) launch<CIN, COUT, 2>(a);
+    else launch<CIN, COUT, 1>(a);
 }
 
 int pick_rg(int64_t n_out, int cin, int cout) {
@@ -265,15 +253,9 @@ int pick_rg(int64_t n_out, int cin, int cout) {
 
 }  // namespace
 
-// fp32 32 -> 32: the 32x32x2 fragment layout of fd_spconv_c32.hip follows the 16x16x4 one in the same buffer
-inline bool has_c32_layout(int cin, int cout, int dtype) { return dtype == 0 && cout == 32 && cin == 32; }
-// bf16 with 16 input channels: the tap-pair layout of fd_spconv_bf16.hip (two taps stacked along K = 32) follows the 16x16x16 one
-inline int64_t pair_layout_elems(int K, int cin, int cout, int dtype) { return (dtype == 1 && cin == 16) ? (int64_t)((K + 1) / 2) * 32 * cout : 0; }
-
 extern "C" size_t fd_spconv_packed_weight_bytes(int K, int cin, int cout, int dtype) {
     if (K <= 0 || cin <= 0 || cout <= 0) return 0;
-    return (size_t)K * cin * cout * (dtype == 0 ? 4 : 2) * (has_c32_layout(cin, cout, dtype) ? 2 : 1) + (size_t)pair_layout_elems(K, cin, cout, dtype) * 2 +
-           (dtype == 1 ? fd::spconv_bf16_win_weight_bytes(K, cin, cout) : 0);
+    return fd::spconv_weight_layout(K, cin, cout, dtype).total;
 }
 
 extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, int dtype, void *dst) {
@@ -283,6 +265,7 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
                "fd_spconv_pack_weight: channels must be multiples of 16 in [16,128] (got %d -> %d)", cin, cout);
     FD_REQUIRE(dtype == 0 || dtype == 1, "fd_spconv_pack_weight: dtype must be 0 (f32) or 1 (bf16)");
     const int NB = cout / 16;
+    const fd::SpconvWeightLayout lay = fd::spconv_weight_layout(K, cin, cout, dtype);
     auto W = [&](int k, int ci, int co) { return w[((int64_t)k * cin + ci) * cout + co]; };
     auto tobf = [](float v) -> uint16_t {
         union { float f; uint32_t u; } cvt;
@@ -301,8 +284,8 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
                         for (int j = 0; j < 4; ++j)
                             d[((((int64_t)k * NC + c) * NB + nb) * 64 + lane) * 4 + j] =
                                 W(k, 16 * c + 4 * (lane >> 4) + j, 16 * nb + (lane & 15));
-        if (has_c32_layout(cin, cout, dtype)) {  // [K][cin / 8][lane][4]: channel 8 c + 4 (lane / 32) + j, output channel lane % 32
-            float *e = d + (int64_t)K * cin * cout;
+        if (lay.c32.bytes) {  // [K][cin / 8][lane][4]: channel 8 c + 4 (lane / 32) + j, output channel lane % 32
+            float *e = (float *)((char *)dst + lay.c32.offset);
             for (int k = 0; k < K; ++k)
                 for (int c = 0; c < cin / 8; ++c)
                     for (int lane = 0; lane < 64; ++lane)
@@ -321,7 +304,7 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
                             d[((((int64_t)k * NC + c) * NB + nb) * 64 + lane) * 8 + j] =
                                 tobf(W(k, 32 * c + 8 * (lane >> 4) + j, 16 * nb + (lane & 15)));
         // the LDS-window kernel's 32x32x16 fragment order follows (fd_spconv_bf16win.hip)
-        if (fd::spconv_bf16_win_weight_bytes(K, cin, cout)) fd::spconv_bf16_win_pack(w, K, cin, cout, +tobf, d + (int64_t)K * cin * cout);
+        if (lay.win.bytes) fd::spconv_bf16_win_pack(w, K, cin, cout, +tobf, (uint16_t *)((char *)dst + lay.win.offset));
     } else {
         uint16_t *d = (uint16_t *)dst;
         for (int k = 0; k < K; ++k)
@@ -330,7 +313,7 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
                     for (int j = 0; j < 4; ++j)
                         d[(((int64_t)k * NB + nb) * 64 + lane) * 4 + j] = tobf(W(k, 4 * (lane >> 4) + j, 16 * nb + (lane & 15)));
         // tap pairs [ceil(K/2)][NB][lane][8]: quads 0,1 = channels 0..7 / 8..15 of tap 2u, quads 2,3 = those of tap 2u + 1 (zeros past K)
-        uint16_t *e = d + (int64_t)K * cin * cout;
+        uint16_t *e = (uint16_t *)((char *)dst + lay.pair.offset);
         for (int u = 0; u < (K + 1) / 2; ++u)
             for (int nb = 0; nb < NB; ++nb)
                 for (int lane = 0; lane < 64; ++lane)
@@ -352,63 +335,44 @@ extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *w
     if (n_expected <= 0 || n_expected > n_out) n_expected = n_out;  // only steers launch heuristics
     if (n_out == 0) return FD_OK;  // an empty active set (empty cloud): nothing to compute, buffers may be null
     FD_REQUIRE(in_feats && wpacked && nbr && out_feats, "fd_spconv_apply: null argument");
+    const fd::SpconvCall c{in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, (int)n_out, n_out_dev, n_expected,
+                           cin, cout, dtype, out_feats, fd::as_stream(stream)};
     if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && cin == 16 && fd::tuning(fd::kTuneF32ResRG) >= 0) {
         // the 16-channel level: resident weights + register accumulators + empty-item skipping (fd_spconv_f32r.hip); "f32_res_rg" = -1
         // keeps the pair-compacting kernel for A/B runs
-        if (fd::spconv_f32_res16_dispatch((const float *)in_feats, wpacked, bias, (const float *)residual, relu, nbr, nbr_stride, K, n_in, (int)n_out,
-                                          n_out_dev, n_expected, cin, cout, (float *)out_feats, fd::as_stream(stream)))
-            return fd::check_launch("fd_spconv_apply(f32 resident)");
+        if (fd::spconv_f32_res16_dispatch(c)) return fd::check_launch("fd_spconv_apply(f32 resident)");
     }
-    if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && has_c32_layout(cin, cout, dtype) && fd::tuning(fd::kTuneSpconvC32) >= 0) {
-        // 32-column layers: 32-pair items on the 32x32x2 MFMA (fd_spconv_c32.hip); its weight layout follows the 16x16x4 one
-        const void *w32 = (const char *)wpacked + (size_t)K * cin * cout * 4;
-        if (fd::spconv_f32_c32_dispatch((const float *)in_feats, w32, bias, (const float *)residual, relu, nbr, nbr_stride, K, n_in, (int)n_out,
-                                        n_out_dev, cin, cout, (float *)out_feats, ranges, n_ranges, fd::as_stream(stream)))
-            return fd::check_launch("fd_spconv_apply(c32)");
+    if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && fd::tuning(fd::kTuneSpconvC32) >= 0) {
+        // 32 -> 32: 32-pair items on the 32x32x2 MFMA (fd_spconv_c32.hip)
+        if (fd::spconv_f32_c32_dispatch(c)) return fd::check_launch("fd_spconv_apply(c32)");
     }
     if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1)) {
         // fp32 is MFMA-bound: the pair-compacting kernel (fd_spconv_v2.hip) feeds the matrix core no zero rows
-        if (fd::spconv_f32_compact_dispatch((const float *)in_feats, wpacked, bias, (const float *)residual, relu, nbr, nbr_stride, K, n_in,
-                                            (int)n_out, n_out_dev, cin, cout, (float *)out_feats, ranges, n_ranges, fd::as_stream(stream)))
-            return fd::check_launch("fd_spconv_apply(compact)");
+        if (fd::spconv_f32_compact_dispatch(c)) return fd::check_launch("fd_spconv_apply(compact)");
     }
     if (dtype == 1 && fd::tuning(fd::kTuneBf16GP) >= 0) {
-        // bf16: register accumulators + LDS-shared weights (fd_spconv_bf16.hip); 16 input channels read the tap-pair weight layout
-        const void *w = cin == 16 ? (const void *)((const char *)wpacked + (size_t)K * cin * cout * 2) : wpacked;
         // 64 -> 64, 128 -> 128 (the SubM layers of levels 2 and 3): LDS window of input rows + 32-row register tiles
         // (fd_spconv_bf16win.hip); "bf16_win" = -1 keeps the RING / RESIDENT kernels (A/B runs, variant tests)
         // The window [row - HALO, row + TM + HALO] only holds the neighbours when input rows lie around the output rows, i.e. for a SubM
         // convolution (27 taps over the SAME row set).  The strided 128 -> 128 extra_conv (K = 3, stride (2,1,1)) has the shape but not the
         // property: every lane would take the exec-masked global gather next to a window staged for nothing -> RING kernel.
-        // ("bf16_win" = 2 / FD_BF16_WIN=2 sends such a layer to the window kernel all the same: the A/B of this rule)
-        const bool subm_like = (K == 27 && n_in == n_out) || fd::tuning(fd::kTuneBf16Win) == 2;
-        if (fd::tuning(fd::kTuneBf16Win) >= 0 && subm_like && fd::spconv_bf16_win_weight_bytes(K, cin, cout) &&
-            fd::spconv_bf16_win_dispatch(in_feats, (const char *)wpacked + (size_t)K * cin * cout * 2, bias, residual, relu, nbr, nbr_stride, K, n_in, (int)n_out,
-                                         n_out_dev, n_expected, cin, cout, out_feats, fd::as_stream(stream)))
-            return fd::check_launch("fd_spconv_apply(bf16 window)");
-        if (fd::spconv_bf16_ws_dispatch(in_feats, w, bias, residual, relu, nbr, nbr_stride, K, n_in, (int)n_out, n_out_dev, n_expected, cin, cout, out_feats,
-                                        fd::as_stream(stream)))
-            return fd::check_launch("fd_spconv_apply(bf16 ws)");
-        // "strict" (fd_tuning_set / FD_STRICT=1; tests and tuning runs): a shape the default kernel family covers must not fall
-        // through to the older kernels silently (round 3: 32 -> 64 did, because its LDS request did not fit)
-        if (fd::tuning(fd::kTuneStrict) && n_in * cin * 2 < (1ll << 31)) {
-            fd::set_error("fd_spconv_apply: strict mode: the bf16 kernel (fd_spconv_bf16.hip) did not take %d -> %d, K = %d", cin, cout, K);
-            return FD_EINVAL;
-        }
+        const bool subm_like = K == 27 && n_in == n_out;
+        if (fd::tuning(fd::kTuneBf16Win) >= 0 && subm_like && fd::spconv_bf16_win_dispatch(c)) return fd::check_launch("fd_spconv_apply(bf16 window)");
+        // register accumulators + LDS-shared weights (fd_spconv_bf16.hip)
+        if (fd::spconv_bf16_ws_dispatch(c)) return fd::check_launch("fd_spconv_apply(bf16 ws)");
     }
     // what is left below: the register-resident output-stationary kernels of round 1 -- the path for feature matrices of 2 GB and
     // more (the kernels above address rows through 32-bit buffer offsets) and the A/B partner of the variant tests
-    LaunchArgs a{in_feats, wpacked, bias, residual, relu, nbr, nbr_stride, K, (int)n_out, n_out_dev, out_feats, fd::as_stream(stream)};
     const int rg = pick_rg(n_expected, cin, cout);
     const int key = cin * 1000 + cout;
     switch (key) {
-        case 16016: launch_rg<16, 16>(a, dtype, rg); break;
-        case 16032: launch_rg<16, 32>(a, dtype, rg); break;
-        case 32032: launch_rg<32, 32>(a, dtype, rg); break;
-        case 32064: launch_rg<32, 64>(a, dtype, rg); break;
-        case 64064: launch_rg<64, 64>(a, dtype, rg); break;
-        case 64128: launch_rg<64, 128>(a, dtype, rg); break;
-        case 128128: launch_rg<128, 128>(a, dtype, rg); break;
+        case 16016: launch_rg<16, 16>(c, rg); break;
+        case 16032: launch_rg<16, 32>(c, rg); break;
+        case 32032: launch_rg<32, 32>(c, rg); break;
+        case 32064: launch_rg<32, 64>(c, rg); break;
+        case 64064: launch_rg<64, 64>(c, rg); break;
+        case 64128: launch_rg<64, 128>(c, rg); break;
+        case 128128: launch_rg<128, 128>(c, rg); break;
         default:
             fd::set_error("fd_spconv_apply: unsupported channels %d -> %d", cin, cout);
             return FD_EINVAL;

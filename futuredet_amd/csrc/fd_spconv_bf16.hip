@@ -340,21 +340,6 @@ __global__ void __launch_bounds__(NW * 64) spconv_bf16_ws(const unsigned short *
     }
 }
 
-struct WsArgs {
-    const void *in, *wp;
-    const float *bias;
-    const void *residual;
-    int relu;
-    const int *nbr;
-    int64_t nbr_stride;
-    int K, n_out;
-    const int *n_out_dev;
-    void *out;
-    unsigned in_bytes;
-    int64_t n_expected;
-    hipStream_t stream;
-};
-
 template <int CIN, int COUT, int RG, int NW, bool RING>
 constexpr size_t ws_lds_bytes(int K) {
     const int T = CIN == 16 ? (K + 1) / 2 : K;
@@ -388,7 +373,7 @@ struct WsKernel {
         return nb;
     }
     static int64_t rows_per_round(int K) { return (int64_t)wgs_per_cu(K) * fd::device_cu_count() * NW * 16 * RG; }  // rows all resident workgroups cover in one pass
-    static bool launch(const WsArgs &a) {
+    static bool launch(const fd::SpconvCall &a) {
         const int wpc = wgs_per_cu(a.K);
         if (wpc <= 0) return false;
         // persistent workgroups, as many as the device holds at once; fewer when the level is small (a capacity launch is
@@ -399,8 +384,12 @@ struct WsKernel {
         if (grid > cap) grid = cap;
         if (grid < 1) grid = 1;
         const size_t lds = ws_lds_bytes<CIN, COUT, RG, NW, RING>(a.K);
-        hipLaunchKernelGGL((spconv_bf16_ws<CIN, COUT, RG, DEPTH, NW, RING>), dim3((unsigned)grid), dim3(NW * 64), lds, a.stream, (const unsigned short *)a.in, (const u32x4 *)a.wp, a.bias, (const unsigned short *)a.residual, a.relu, a.nbr, a.nbr_stride,
-                           a.K, a.n_out, a.n_out_dev, (unsigned short *)a.out, a.in_bytes, (!RING && fd::tuning(fd::kTuneBf16NW) != 1) ? 1 : 0);
+        const unsigned in_bytes = (unsigned)(a.n_in * CIN * 2);
+        // 16 input channels read the tap-pair weight layout
+        const fd::SpconvWeightLayout lay = fd::spconv_weight_layout(a);
+        const void *wp = (const char *)a.wpacked + (CIN == 16 ? lay.pair : lay.base).offset;
+        hipLaunchKernelGGL((spconv_bf16_ws<CIN, COUT, RG, DEPTH, NW, RING>), dim3((unsigned)grid), dim3(NW * 64), lds, a.stream, (const unsigned short *)a.in, (const u32x4 *)wp, a.bias, (const unsigned short *)a.residual, a.relu, a.nbr, a.nbr_stride,
+                           a.K, a.n_out, a.n_out_dev, (unsigned short *)a.out, in_bytes, (!RING && fd::tuning(fd::kTuneBf16NW) != 1) ? 1 : 0);
         // RESIDENT kernels: tiles interleaved over the grid -- all workgroups sweep the row range together (round 6, in the config-3 sweep: 32 -> 32
         // 280.5 -> 274.2 us, 16 -> 16 88.5 -> 83.3, 32 -> 64 71.1 -> 67.7, 16 -> 32 46.8 -> 42.4 per two-cloud pass; "bf16_nw" = 1 brings the
         // XCD-contiguous chunks back for A/B runs).  RING kernels keep their contiguous row ranges per workgroup.
@@ -411,7 +400,7 @@ struct WsKernel {
 // RESIDENT shapes (the whole weight set in LDS, 16 free-running waves per workgroup): rg in {1, 2, 4}; the register file of a
 // 1024-thread workgroup (128 per lane) excludes 4 row groups for 64 output columns and the deep ring next to 4 groups.
 template <int CIN, int COUT>
-bool launch_resident(const WsArgs &a, int rg, int depth) {
+bool launch_resident(const fd::SpconvCall &a, int rg, int depth) {
     if constexpr (CIN == 32 && COUT == 64) {
         // 27 taps x 4 KB of weights = 108 KB: next to them only 8 waves' rulebook slices fit the CU's 160 KB (16 waves: 166 KB --
         // that variant refused every K = 27 launch of round 3 and the layer silently ran the round-2 kernel).  512-thread
@@ -436,7 +425,7 @@ bool launch_resident(const WsArgs &a, int rg, int depth) {
 // row groups per wave with which the resident workgroups cover the level in ONE pass (a second, partly empty pass would cost
 // a whole walk over the taps), else the largest.
 template <int CIN, int COUT>
-bool launch_ring(const WsArgs &a, int rg, int depth) {
+bool launch_ring(const fd::SpconvCall &a, int rg, int depth) {
     constexpr int kMaxRG = COUT > 64 ? 2 : 4;  // (128 output columns: 3 row groups spill)
     if (rg <= 0) {
         const int64_t n = a.n_expected;
@@ -445,11 +434,6 @@ bool launch_ring(const WsArgs &a, int rg, int depth) {
         else if (kMaxRG >= 3 && WsKernel<CIN, COUT, kMaxRG >= 3 ? 3 : 2, 2, 8, true>::rows_per_round(a.K) >= n) rg = 3;
         else rg = kMaxRG >= 4 ? 3 : kMaxRG;  // two passes either way: three row groups per wave (384-row passes) measured best on
                                               // 64 -> 64 at 155k rows (68 us; rg 2: 72, rg 4: 79 -- tools/spconv_bench.py, round 4)
-    }
-    if (fd::tuning(fd::kTuneBf16NW) == 4) {  // experiment: 4-wave workgroups (two per CU, barriers decoupled), rg row groups per wave
-        if (rg >= 4) return WsKernel<CIN, COUT, 4, 2, 4, true>::launch(a);
-        if (rg >= 3) return WsKernel<CIN, COUT, 3, 2, 4, true>::launch(a);
-        return WsKernel<CIN, COUT, 2, 2, 4, true>::launch(a);
     }
     if constexpr (kMaxRG >= 4) {
         if (rg >= 4) return WsKernel<CIN, COUT, 4, 2, 8, true>::launch(a);
@@ -466,10 +450,9 @@ bool launch_ring(const WsArgs &a, int rg, int depth) {
 
 namespace fd {
 // returns 1 when launched, 0 when the shape is not covered (caller falls back to the older kernels)
-int spconv_bf16_ws_dispatch(const void *in, const void *wp, const float *bias, const void *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                            int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, void *out, hipStream_t stream) {
-    if (n_in_bound * cin * 2 >= (1ll << 31)) return 0;  // the 'missing neighbour' offset must lie beyond the buffer
-    WsArgs a{in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, (unsigned)(n_in_bound * cin * 2), n_expected, stream};
+int spconv_bf16_ws_dispatch(const SpconvCall &a) {
+    const int cin = a.cin, cout = a.cout;
+    if (a.n_in * cin * 2 >= (1ll << 31)) return 0;  // the 'missing neighbour' offset must lie beyond the buffer
     int rg = fd::tuning(fd::kTuneBf16RG), depth = fd::tuning(fd::kTuneBf16Depth);  // 0 = the heuristics below
     const bool ring = cin * cout > 32 * 64;
     if (!ring) {

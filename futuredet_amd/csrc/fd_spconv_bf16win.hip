@@ -11,7 +11,7 @@
 //   (b) LDS bytes per MFMA: a wave owned 16-48 rows and read the whole W[tap] from LDS for them -- eight waves, all at the same
 //       moment behind the tap barrier.
 // Round 4's window kernel removed (a) and made (b) worse (16 rows per wave); this one does both:
-//   * a workgroup = NW waves (8: two per SIMD, half the register file each; 4: one per SIMD, "bf16_nw") owns TM = NW * 32 * RGS
+//   * a workgroup = NW waves (8: two per SIMD, half the register file each) owns TM = NW * 32 * RGS
 //     consecutive output rows per pass and stages the input rows [first - HALO, last + HALO] ONCE, by LDS-DMA (global_load_lds_dwordx4:
 //     no registers, no ds_write), 16-byte pieces XOR-swizzled by the row.  Rows are spatially sorted (fd_index.hip), so 90 % of all
 //     pairs lie inside; a (32-row group, tap) item with a neighbour outside takes the bounds-checked global gather for its lanes
@@ -450,23 +450,8 @@ __global__ void __launch_bounds__(NW * 64) spconv_bf16_win(const unsigned short 
 #endif
 }
 
-struct WinArgs {
-    const void *in, *wp;
-    const float *bias;
-    const void *residual;
-    int relu;
-    const int *nbr;
-    int64_t nbr_stride;
-    int K, n_out;
-    const int *n_out_dev;
-    void *out;
-    unsigned in_bytes;
-    int n_in;
-    hipStream_t stream;
-};
-
-template <int CIN, int COUT, int RGS, int HALO, int NW = 4>
-bool win_launch(const WinArgs &a) {
+template <int CIN, int COUT, int RGS, int HALO, int NW>
+bool win_launch(const fd::SpconvCall &a) {
     constexpr int kWaves = NW;
     constexpr size_t lds = win_lds_bytes<CIN, COUT, RGS, HALO, NW>();
     static_assert(lds <= 160 * 1024, "window + weight ring must fit the CU's LDS");
@@ -478,15 +463,17 @@ bool win_launch(const WinArgs &a) {
     const int64_t cus = fd::device_cu_count();  // one workgroup per CU (LDS), persistent over its passes
     if (grid > cus) grid = cus;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWaves * 64), lds, a.stream, (const unsigned short *)a.in, (const unsigned char *)a.wp, a.bias,
-                       (const unsigned short *)a.residual, a.relu, a.nbr, a.nbr_stride, a.K, a.n_out, a.n_out_dev, (unsigned short *)a.out, a.in_bytes,
-                       a.n_in);
+    const unsigned in_bytes = (unsigned)(a.n_in * CIN * 2);
+    const void *wp = (const char *)a.wpacked + fd::spconv_weight_layout(a).win.offset;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kWaves * 64), lds, a.stream, (const unsigned short *)a.in, (const unsigned char *)wp, a.bias,
+                       (const unsigned short *)a.residual, a.relu, a.nbr, a.nbr_stride, a.K, a.n_out, a.n_out_dev, (unsigned short *)a.out, in_bytes,
+                       (int)a.n_in);
     return true;
 }
 
 // row groups per wave: the fewest with which one pass of the resident workgroups covers the level; beyond the largest tile the
 // rows are spread evenly over the passes (a last pass with a few rows costs a whole walk over the taps)
-inline int pick_rgs(int64_t n_expected, int rgs_max, int kWaves = 4) {
+inline int pick_rgs(int64_t n_expected, int rgs_max, int kWaves) {
     const int64_t cus = fd::device_cu_count();
     const int64_t per_cu = (n_expected + cus - 1) / cus;
     const int64_t tm_max = (int64_t)kWaves * 32 * rgs_max;
@@ -503,12 +490,6 @@ extern "C" int fd_debug_set_wintrace(void *p) { return hipMemcpyToSymbol(HIP_SYM
 #endif
 
 namespace fd {
-// bytes of the window kernels' weight layout for (K, cin, cout); 0 = shape not covered
-size_t spconv_bf16_win_weight_bytes(int K, int cin, int cout) {
-    if (!((cin == 64 && cout == 64) || (cin == 128 && cout == 128))) return 0;
-    return (size_t)K * cin * cout * 2;
-}
-
 // [K][H halves][KS k-steps][CB column blocks][lane][8] bf16: lane (m = lane % 32, kg = lane / 32) element j of fragment
 // (tap, h, s, cb) = W[tap][input channel SC h + 16 s + 8 kg + j][output channel 32 cb + m] -- the A operand of v_mfma_f32_32x32x16_bf16
 void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*tobf)(float), uint16_t *dst) {
@@ -525,33 +506,19 @@ void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*t
 }
 
 // returns 1 when launched, 0 when the shape is not covered (the caller takes the RING / RESIDENT kernels)
-int spconv_bf16_win_dispatch(const void *in, const void *wp_win, const float *bias, const void *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                             int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, void *out, hipStream_t stream) {
-    if (n_in_bound * cin * 2 >= (1ll << 31) || n_in_bound < 1 || K < 1 || K > kMaxTaps) return 0;
-    WinArgs a{in, wp_win, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, (unsigned)(n_in_bound * cin * 2), (int)n_in_bound, stream};
-    const int forced = fd::tuning(fd::kTuneBf16RG);  // 0 = heuristic
+int spconv_bf16_win_dispatch(const SpconvCall &a) {
+    if (!spconv_weight_layout(a).win.bytes) return 0;
+    if (a.n_in * a.cin * 2 >= (1ll << 31) || a.n_in < 1 || a.K < 1 || a.K > kMaxTaps) return 0;
     bool ok = false;
     // Eight waves (two per SIMD, 256 registers each, one or two 32-row groups) against four (one per SIMD, up to four groups): with two
     // waves a SIMD's matrix pipe is fed while the other wave sits in an LDS / vector-memory wait -- 59 vs 64 us on 128 -> 128, 64 vs 67-75 on
     // 64 -> 64 (tools/spconv_bench.py, round 5) although every weight fragment read from LDS then feeds half as many MFMAs.
-    // "bf16_nw" = 4 selects the four-wave shapes (A/B runs).
-    const bool nw4 = fd::tuning(fd::kTuneBf16NW) == 4;
-    if (cin == 128 && cout == 128 && !nw4) {
+    if (a.cin == 128 && a.cout == 128) {
         ok = win_launch<128, 128, 1, 64, 8>(a);
-    } else if (cin == 64 && cout == 64 && !nw4) {
-        const int rgs = forced > 0 ? (forced > 2 ? 2 : forced) : pick_rgs(n_expected, 2, 8);
+    } else if (a.cin == 64 && a.cout == 64) {
+        const int forced = fd::tuning(fd::kTuneBf16RG);  // 0 = heuristic
+        const int rgs = forced > 0 ? (forced > 2 ? 2 : forced) : pick_rgs(a.n_expected, 2, 8);
         ok = rgs >= 2 ? win_launch<64, 64, 2, 128, 8>(a) : win_launch<64, 64, 1, 128, 8>(a);
-    } else if (cin == 128 && cout == 128) {
-        const int rgs = forced > 0 ? (forced > 2 ? 2 : forced) : pick_rgs(n_expected, 2);
-        ok = rgs >= 2 ? win_launch<128, 128, 2, 64>(a) : win_launch<128, 128, 1, 64>(a);
-    } else if (cin == 64 && cout == 64) {
-        const int rgs = forced > 0 ? (forced > 4 ? 4 : forced) : pick_rgs(n_expected, 4);  // (5 row groups spill: 160 + 160 accumulator / operand registers)
-        switch (rgs) {
-            case 1: ok = win_launch<64, 64, 1, 128>(a); break;
-            case 2: ok = win_launch<64, 64, 2, 128>(a); break;
-            case 3: ok = win_launch<64, 64, 3, 128>(a); break;
-            default: ok = win_launch<64, 64, 4, 128>(a); break;
-        }
     }
     // (32 -> 32 on this formulation -- a weight ring with a barrier per tap -- measured 66 us against the 42 us of the RESIDENT kernel of
     //  fd_spconv_bf16.hip; a second form with the weight set resident in LDS, a sliding window and no barrier inside a pass was built,

@@ -152,30 +152,26 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
 }
 
 template <int CIN, int DEPTH>
-int launch_c32(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-               int n_out, const int *n_out_dev, float *out, unsigned in_bytes, const int *ranges, int n_ranges, hipStream_t stream) {
-    int rows_per = 0;
-    if (!ranges) sk::equal_rows_split(n_out, TM, n_out_dev != nullptr, n_ranges, rows_per);
+int launch_c32(const fd::SpconvCall &c) {
+    const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
+    int n_ranges = c.n_ranges, rows_per = 0;
+    if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its dynamic-LDS limit raised (> 64 KB)
     if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(spconv_f32_c32<CIN, DEPTH>), (size_t)L.bytes, lds_set)) return 0;
-    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, stream, in, (const float4 *)wp, bias, residual, relu,
-                       nbr, nbr_stride, K, n_out, n_out_dev, out, in_bytes, ranges, rows_per);
+    // the 32x32x2 fragment layout ([K][CIN / 8][64 lanes] float4, see fd_spconv_pack_weight)
+    const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).c32.offset;
+    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, c.stream, (const float *)c.in, (const float4 *)wp,
+                       c.bias, (const float *)c.residual, c.relu, c.nbr, c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }
 
 }  // namespace
 
 namespace fd {
-// wp: the 32x32x2 fragment layout ([K][CIN / 8][64 lanes] float4, see fd_spconv_pack_weight).  Returns 1 when launched.
-int spconv_f32_c32_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride,
-                            int K, int64_t n_in_bound, int n_out, const int *n_out_dev, int cin, int cout, float *out, const int *ranges,
-                            int n_ranges, hipStream_t stream) {
-    if (cout != 32 || cin != 32) return 0;
-    if (!sk::entries_fit(n_in_bound, cin)) return 0;
-    const unsigned in_bytes = (unsigned)(n_in_bound * cin * 4);
-    const int depth = fd::tuning(fd::kTuneV2Depth);
-    if (depth == 2) return launch_c32<32, 2>(in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, in_bytes, ranges, n_ranges, stream);
-    if (depth == 4) return launch_c32<32, 4>(in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, in_bytes, ranges, n_ranges, stream);
-    return launch_c32<32, 3>(in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, in_bytes, ranges, n_ranges, stream);
+// Returns 1 when launched.
+int spconv_f32_c32_dispatch(const SpconvCall &c) {
+    if (c.cout != 32 || c.cin != 32) return 0;
+    if (!sk::entries_fit(c.n_in, c.cin)) return 0;
+    return launch_c32<32, 3>(c);
 }
 }  // namespace fd

@@ -211,8 +211,7 @@ __global__ void __launch_bounds__(NW * 64) spconv_f32_res16(const float *__restr
 }
 
 template <int COUT, int RG, int DEPTH, int NW>
-int launch_res16(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride, int K, int n_out,
-                 const int *n_out_dev, int64_t n_expected, float *out, unsigned in_bytes, hipStream_t stream) {
+int launch_res16(const fd::SpconvCall &c) {
     constexpr size_t lds = (size_t)kMaxTaps * (COUT / 16) * 1024 + (size_t)NW * (2 * (kMaxTaps + 1) + 1) * 16 * RG * 4;
     static_assert(lds <= 160 * 1024, "LDS request");
     constexpr int per_cu = (int)((160 * 1024) / lds) < 32 / NW ? (int)((160 * 1024) / lds) : 32 / NW;  // resident workgroups per CU (LDS, 32 waves)
@@ -220,12 +219,14 @@ int launch_res16(const float *in, const void *wp, const float *bias, const float
     static std::atomic<uint64_t> lds_set{0};
     if (lds > 65536 && !fd::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds, lds_set)) return 0;
     constexpr int64_t wg_rows = NW * 16 * RG;
-    int64_t grid = (n_expected + wg_rows - 1) / wg_rows;
+    int64_t grid = (c.n_expected + wg_rows - 1) / wg_rows;
     const int64_t cap = (int64_t)fd::device_cu_count() * (per_cu > 0 ? per_cu : 1);  // persistent workgroups, every resident slot of every CU
     if (grid > cap) grid = cap;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, stream, in, (const f32x4 *)wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev,
-                       out, in_bytes, fd::tuning(fd::kTuneF32ResNW) == 1 ? 0 : 1);
+    const unsigned in_bytes = (unsigned)(c.n_in * 64);
+    const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).base.offset;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, c.stream, (const float *)c.in, (const f32x4 *)wp, c.bias, (const float *)c.residual, c.relu,
+                       c.nbr, c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, fd::tuning(fd::kTuneF32ResNW) == 1 ? 0 : 1);
     return 1;
 }
 
@@ -233,19 +234,15 @@ int launch_res16(const float *in, const void *wp, const float *bias, const float
 
 namespace fd {
 // 16 input channels, 16 or 32 output channels.  1 = launched, 0 = not this kernel's shape.
-int spconv_f32_res16_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr, int64_t nbr_stride, int K,
-                              int64_t n_in_bound, int n_out, const int *n_out_dev, int64_t n_expected, int cin, int cout, float *out, hipStream_t stream) {
+int spconv_f32_res16_dispatch(const SpconvCall &c) {
     // 16 -> 32 (the strided convolution into level 1: 272k output rows, 2.4 pairs per row) is the pair-compacting kernel's: measured
     // 63 us here against 44 us there (profiles/round4_serial_step_summary.txt of the first run); "f32_res_rg" >= 32 forces it for A/B runs
-    if (cin != 16 || (cout != 16 && cout != 32) || n_in_bound * 64 >= (1ll << 31)) return 0;
-    if (cout == 32 && fd::tuning(fd::kTuneF32ResRG) < 32) return 0;
-    const unsigned in_bytes = (unsigned)(n_in_bound * 64);
+    if (c.cin != 16 || (c.cout != 16 && c.cout != 32) || c.n_in * 64 >= (1ll << 31)) return 0;
     const int rg = fd::tuning(fd::kTuneF32ResRG);
+    if (c.cout == 32 && rg < 32) return 0;
     // Measured and dropped in round 6 (profiles/round6_tiles_prototype.txt): gather ring depth 8 / 12 / 16 (24.6 -> 26.9 / 28.2 / 32.1 us), two workgroups of 14
     // waves per CU (29.4 vs 27.3 us), two row groups per wave with interleaved tiles (43.6 vs 41.1 us on two clouds).
-#define FD_RES(CO, RGV) launch_res16<CO, RGV, 4, 16>(in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, n_expected, out, in_bytes, stream)
-    if (cout == 16) return rg >= 2 ? FD_RES(16, 2) : FD_RES(16, 1);
-    return FD_RES(32, 1);
-#undef FD_RES
+    if (c.cout == 16) return rg >= 2 ? launch_res16<16, 2, 4, 16>(c) : launch_res16<16, 1, 4, 16>(c);
+    return launch_res16<32, 1, 4, 16>(c);
 }
 }  // namespace fd

@@ -296,8 +296,9 @@ extern "C" int fd_spconv_pack_weight_device(const float *w_kio, int K, int cin, 
                "fd_spconv_pack_weight_device: channels must be multiples of 16 in [16,128] (got %d -> %d)", cin, cout);
     FD_REQUIRE(mode >= 0 && mode <= 2, "fd_spconv_pack_weight_device: mode must be 0 (W[k]), 1 (W[k]^T) or 2 (W[K-1-k]^T)");
     const int ci = mode ? cout : cin, co = mode ? cin : cout;
-    const int c32 = ci == 32 && co == 32;
-    const int64_t n = (int64_t)K * ci * co * (c32 ? 2 : 1);
+    const fd::SpconvWeightLayout lay = fd::spconv_weight_layout(K, ci, co, 0);  // the kernel writes base, then c32 right behind it
+    const int c32 = lay.c32.bytes != 0;
+    const int64_t n = (int64_t)(lay.total / sizeof(float));
     hipLaunchKernelGGL(pack_weight_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fd::as_stream(stream_), w_kio, K, cin, cout, mode, ci, co, c32,
                        (float *)wpacked);
     return fd::check_launch("fd_spconv_pack_weight_device");

@@ -275,30 +275,21 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
 // their request is rounded up to just over a third of the CU's 160 KB.
 inline size_t lds_request(int cin, int cout, int tm) {
     const size_t lds = (size_t)sk::layout(tm, cout, tap_splits(cout), 16).bytes;
-    const size_t pad = (size_t)fd::tuning(fd::kTuneV2LdsPad);  // occupancy experiments
-    if (pad) return lds + pad;
     return (cin == 64 && cout == 64 && tm == 128 && lds < 56 * 1024) ? (size_t)56 * 1024 : lds;
 }
 
 template <int CIN, int COUT, int TM, int DEPTH>
-int launch_compact(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr,
-                   int64_t nbr_stride, int K, int n_out, const int *n_out_dev, float *out, unsigned in_bytes, const int *ranges, int n_ranges,
-                   hipStream_t stream) {
+int launch_compact(const fd::SpconvCall &c) {
     const size_t lds_req = lds_request(CIN, COUT, TM);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its LDS limit raised
     auto kern = spconv_f32_compact<CIN, COUT, TM, DEPTH>;
-    if (fd::tuning(fd::kTuneV2LdsPad)) {  // tuning runs change the request between calls: set it every time
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_req) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0;
-        }
-    } else if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_req, lds_set)) {
-        return 0;
-    }
-    int rows_per = 0;
-    if (!ranges) sk::equal_rows_split(n_out, TM, n_out_dev != nullptr, n_ranges, rows_per);
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_ranges), dim3(256), lds_req, stream, in, (const float4 *)wp, bias, residual, relu, nbr, nbr_stride, K,
-                       n_out, n_out_dev, out, in_bytes, ranges, rows_per);
+    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_req, lds_set)) return 0;
+    const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
+    int n_ranges = c.n_ranges, rows_per = 0;
+    if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
+    const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).base.offset;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_ranges), dim3(256), lds_req, c.stream, (const float *)c.in, (const float4 *)wp, c.bias,
+                       (const float *)c.residual, c.relu, c.nbr, c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }
 
@@ -479,7 +470,7 @@ extern "C" int fd_spconv_num_ranges(int64_t n_out, int cin, int cout, int dtype)
 }
 
 // 1 when the layer shape profits from equal-work ranges (fd_spconv_ranges), 0 when equal rows are the better split
-extern "C" int fd_spconv_wants_balanced_ranges(int cin, int cout, int dtype) { return dtype == 0 && cout >= 64 && !fd::tuning(fd::kTuneV2Uniform); }
+extern "C" int fd_spconv_wants_balanced_ranges(int cin, int cout, int dtype) { return dtype == 0 && cout >= 64; }
 
 extern "C" size_t fd_spconv_ranges_workspace_bytes(int64_t n_out) {
     return fd::align_up(sizeof(unsigned) * (size_t)((n_out + kWorkRows - 1) / kWorkRows + 8), 256);
@@ -495,46 +486,30 @@ extern "C" int fd_spconv_ranges(const int32_t *nbr, int64_t nbr_stride, int K, i
     unsigned *work = (unsigned *)workspace;
     if (n_blocks > 0)
         hipLaunchKernelGGL(block_work_kernel, dim3((unsigned)((n_blocks + 31) / 32)), dim3(256), 0, stream, nbr, nbr_stride, K, (int)n_out, n_out_dev,
-                           (unsigned)(fd::tuning(fd::kTuneV2RowCost) ? fd::tuning(fd::kTuneV2RowCost) : kRowCost), work);
+                           (unsigned)kRowCost, work);
     hipLaunchKernelGGL(range_split_kernel, dim3(1), dim3(1024), 0, stream, work, (int)n_out, n_out_dev, n_ranges, ranges);
     return fd::check_launch("fd_spconv_ranges");
 }
 
 namespace fd {
 // returns 1 when launched, 0 when this shape is not covered (caller falls back to the register kernel)
-int spconv_f32_compact_dispatch(const float *in, const void *wp, const float *bias, const float *residual, int relu, const int *nbr,
-                                int64_t nbr_stride, int K, int64_t n_in_bound, int n_out, const int *n_out_dev, int cin, int cout, float *out,
-                                const int *ranges, int n_ranges, hipStream_t stream) {
-    if (!sk::entries_fit(n_in_bound, cin)) return 0;
-    const unsigned in_bytes = (unsigned)(n_in_bound * cin * 4);
-    const int dsel = fd::tuning(fd::kTuneV2Depth), tsel = fd::tuning(fd::kTuneV2TM);  // tuning overrides
-#define FD_LAUNCH(CI, CO, T, D) \
-    launch_compact<CI, CO, T, D>(in, wp, bias, residual, relu, nbr, nbr_stride, K, n_out, n_out_dev, out, in_bytes, ranges, n_ranges, stream)
-#define FD_CASE(CI, CO, DDEF, TDEF)                                  \
-    if (cin == CI && cout == CO) {                                   \
-        const int dd = dsel ? dsel : DDEF, tt = tsel ? tsel : TDEF;  \
-        if (tt == 64) {                                              \
-            if (dd <= 2) return FD_LAUNCH(CI, CO, 64, 2);            \
-            if (dd == 3) return FD_LAUNCH(CI, CO, 64, 3);            \
-            return FD_LAUNCH(CI, CO, 64, 4);                         \
-        }                                                            \
-        if (dd <= 2) return FD_LAUNCH(CI, CO, 128, 2);               \
-        if (dd == 3) return FD_LAUNCH(CI, CO, 128, 3);               \
-        return FD_LAUNCH(CI, CO, 128, 4);                            \
+int spconv_f32_compact_dispatch(const SpconvCall &c) {
+    if (!sk::entries_fit(c.n_in, c.cin)) return 0;
+    // <CIN, COUT, chunk height, gather ring depth>: 128-row chunks everywhere; the ring is as deep as the gathered rows leave
+    // registers for (4 up to 32 input channels, 3 at 64, 2 at 128)
+    switch (c.cin * 1000 + c.cout) {
+        case 16016: return launch_compact<16, 16, 128, 4>(c);
+        case 16032: return launch_compact<16, 32, 128, 4>(c);
+        case 32032: return launch_compact<32, 32, 128, 4>(c);
+        case 32064: return launch_compact<32, 64, 128, 4>(c);
+        case 64064: return launch_compact<64, 64, 128, 3>(c);
+        case 64128: return launch_compact<64, 128, 128, 3>(c);
+        case 128128: return launch_compact<128, 128, 128, 2>(c);
+        // the transposed shapes: input gradients of the strided 16 -> 32, 32 -> 64 and 64 -> 128 layers (fd_spconv_grad.hip)
+        case 32016: return launch_compact<32, 16, 128, 4>(c);
+        case 64032: return launch_compact<64, 32, 128, 4>(c);
+        case 128064: return launch_compact<128, 64, 128, 2>(c);
     }
-    FD_CASE(16, 16, 4, 128)
-    FD_CASE(16, 32, 4, 128)
-    FD_CASE(32, 32, 4, 128)
-    FD_CASE(32, 64, 4, 128)
-    FD_CASE(64, 64, 3, 128)
-    FD_CASE(64, 128, 3, 128)
-    FD_CASE(128, 128, 2, 128)
-    // the transposed shapes: input gradients of the strided 16 -> 32, 32 -> 64 and 64 -> 128 layers (fd_spconv_grad.hip)
-    FD_CASE(32, 16, 4, 128)
-    FD_CASE(64, 32, 4, 128)
-    FD_CASE(128, 64, 2, 128)
-#undef FD_CASE
-#undef FD_LAUNCH
     return 0;
 }
 }  // namespace fd

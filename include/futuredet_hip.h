@@ -32,20 +32,20 @@ int fd_abi_version(void); /* 8 (round 6.  7: + fd_forecast_from_detections / fd_
                              * bound -- rows past the last descriptor's row_end are dropped.  8: struct fd_decode_cfg grew by nms_kind /
                              * n_radius / circle_radius (circular NMS) -- callers must zero-initialise the struct) */
 const char *fd_last_error(void);
-/* Tuning / test knobs (no reference counterpart).  0 = built-in heuristic.  Names: "spconv_rg" (rows per wave of the
- * register sparse-conv kernel: 1|2|4), "spconv_v1" (1: fp32 on the register kernel instead of the compacting one),
- * "spconv_bf16_v1", "v2_depth", "v2_tm", "v2_ldspad", "conv_nt" (output channels per workgroup of the bf16 dense conv: 64 | 32),
- * "v2_ranges_per_cu", "v2_uniform", "v2_rowcost", "spconv_c32", "bf16_gp", "bf16_rg", "bf16_depth", "bf16_nw",
- * "strict" (1: a bf16 sparse layer that the gather-pipeline kernels cannot take is an error instead of a fall-back to the register
+/* Tuning / test knobs (no reference counterpart): the reference paths the tests compare bit for bit and against the oracle.
+ * 0 = built-in heuristic; any other name is FD_EINVAL.  Names: "spconv_rg" (rows per wave of the register sparse-conv
+ * kernel: 1|2|4), "spconv_v1" (1: fp32 on the register kernel instead of the compacting one), "spconv_c32" (-1: fp32 32 -> 32 on
+ * the 16-pair compacting kernel instead of the 32-pair one), "v2_ranges_per_cu" (row ranges per compute unit of the compacting
+ * kernels), "f32_res_rg" (-1: 16-channel fp32 layers on the pair-compacting kernel instead of the resident-weights one; 2: two row
+ * groups per wave; 32: 16 -> 32 on it as well), "f32_res_nw" (1: that kernel on XCD-contiguous tile chunks instead of interleaved
+ * tiles), "bf16_gp" (-1: bf16 on the register kernel), "bf16_rg" / "bf16_depth" (row groups per wave / gather-ring depth of the bf16
  * kernels), "bf16_win" (-1: the 64 -> 64 / 128 -> 128 bf16 layers on the RING / RESIDENT kernels instead of the LDS-window
- * kernel of round 5; 2: such a layer on the window kernel even when it is not SubM-like), "bf16_nw" (1: RESIDENT bf16 kernels walk
- * XCD-contiguous tile chunks instead of tiles interleaved over the grid; 4: four-wave window shapes), "f32_res_rg" (-1: 16-channel fp32
- * layers on the pair-compacting kernel instead of the resident-weights one), "f32_res_nw" (1: that kernel on XCD-contiguous tile chunks
- * instead of interleaved tiles), "conv_strip" (1: stride-1 bf16 dense layers on strips of 128
- * consecutive pixels instead of 8 x 16 tiles: faster alone, slower with several sweeps in flight; -1: the ragged grid of 8 x 16
- * tiles instead of the default mixed tiling -- whole 8 x 16 tiles plus edge tiles of other shapes; results identical in all three).  Initial
- * values come from the FD_SPCONV_RG, FD_SPCONV_V1, ... environment variables (FD_ + the upper-case name), read once when the
- * library is loaded; nothing on the launch path calls getenv(). */
+ * kernel), "bf16_nw" (1: RESIDENT bf16 kernels walk XCD-contiguous tile chunks instead of tiles interleaved over the grid),
+ * "conv_nt" (output channels per workgroup of the bf16 dense conv: 64 | 32), "conv_strip" (1: stride-1 bf16 dense layers on strips
+ * of 128 consecutive pixels instead of 8 x 16 tiles: faster alone, slower with several sweeps in flight; -1: the ragged grid of 8 x 16
+ * tiles instead of the default mixed tiling -- whole 8 x 16 tiles plus edge tiles of other shapes; results identical in all three).
+ * Initial values come from the environment variable FD_ + the upper-case name (FD_SPCONV_RG, ...), read once when the library is
+ * loaded; nothing on the launch path calls getenv(). */
 int fd_tuning_set(const char *name, int value);
 
 /* ---------------------------------------------------------------------------------------------------

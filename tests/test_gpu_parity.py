@@ -126,7 +126,7 @@ def test_spconv_apply_vs_oracle(hip, cin, cout, dtype):
     |d| <= tol * max(1, |ref|): fp32 1e-4 (north_star allows 1e-3; an fp32 FMA chain of 27*cin terms lands near 1e-6),
     bf16 (config 3) 2e-2.  Every kernel variant is run: fp32 = the pair-compacting kernel (default) and the
     register-resident kernel at 1 / 2 / 4 row groups per wave; bf16 = the LDS-shared-weights kernel (default; 1-4 row groups per
-    wave x ring depth 2 / 4), the column-split kernel and the register kernel.  Variants of one kernel agree bit for bit;
+    wave x ring depth 2 / 4) and the register kernel, which "bf16_gp" = -1 selects.  Variants of one kernel agree bit for bit;
     different kernels agree within the tolerance."""
     from oracle import ops as oops
 
@@ -148,7 +148,6 @@ def test_spconv_apply_vs_oracle(hip, cin, cout, dtype):
     nbr = src.rulebook(src, (3, 3, 3), (1, 1, 1), (1, 1, 1))
     wpk = hip.pack_spconv_weight(torch.from_numpy(w), tdt).cuda()
     run = lambda: hip.spconv_apply(x, wpk, _dev(bias), nbr, src.n, cout, residual=res, relu=True).float().cpu().numpy()  # noqa: E731
-    v1_knob = "spconv_v1" if dtype == "f32" else "spconv_bf16_v1"
     y_ws, y_ring, y_ring_v = [], None, []
     try:
         y_default = run()
@@ -166,26 +165,30 @@ def test_spconv_apply_vs_oracle(hip, cin, cout, dtype):
             if cin == cout and cin >= 64:  # the RING kernels behind the window kernel: their own variants, bit for bit
                 hip.set_tuning("bf16_win", -1)
                 y_ring = run()
-                for rg in (1, 2, 3):
-                    hip.set_tuning("bf16_rg", rg)
-                    y_ring_v.append(run())
+                for rg in (1, 2, 3, 4):
+                    for depth in (2, 4):  # (the deep ring exists at one row group per wave of 64 -> 64)
+                        hip.set_tuning("bf16_rg", rg)
+                        hip.set_tuning("bf16_depth", depth)
+                        y_ring_v.append(run())
                 hip.set_tuning("bf16_rg", 0)
-            hip.set_tuning("bf16_gp", -1)  # the older kernels: column split (default where it applies) ...
+                hip.set_tuning("bf16_depth", 0)
+            hip.set_tuning("bf16_gp", -1)  # the register kernel (bf16 has no other older family)
             y_old = run()
-        hip.set_tuning(v1_knob, 1)          # ... and the register kernel
+        else:
+            hip.set_tuning("spconv_v1", 1)  # fp32: the register kernel
         ys = []
         for rg in (1, 2, 4):  # every row-group variant of the register kernel
             hip.set_tuning("spconv_rg", rg)
             ys.append(run())
     finally:
         hip.set_tuning("spconv_rg", 0)
-        hip.set_tuning(v1_knob, 0)
+        hip.set_tuning("spconv_v1", 0)
         hip.set_tuning("bf16_rg", 0)
         hip.set_tuning("bf16_depth", 0)
         hip.set_tuning("bf16_gp", 0)
         hip.set_tuning("bf16_win", 0)
     for other in y_ring_v:
-        assert np.array_equal(y_ring, other), "bf16 RING / RESIDENT kernels: rows-per-wave variants must agree bit for bit"
+        assert np.array_equal(y_ring, other), "bf16 RING kernels: rows-per-wave / ring-depth variants must agree bit for bit"
     for other in y_ws:
         assert np.array_equal(y_default, other), "bf16: rows-per-wave / ring-depth variants must agree bit for bit"
     for other in ys[1:]:

@@ -332,6 +332,23 @@ def test_weight_packing_layout():
     assert b"multiples of 16" in L.fd_last_error()
 
 
+def test_tuning_set_accepts_exactly_the_documented_knobs():
+    """fd_tuning_set touches no device: the 13 knobs the tests and the A/B tools use are accepted (set to 0, the heuristic), the
+    seven removed ones and an unknown name are FD_EINVAL with the name in fd_last_error()."""
+    L = lib.load()
+    kept = ["spconv_rg", "spconv_v1", "spconv_c32", "f32_res_rg", "f32_res_nw", "bf16_gp", "bf16_rg", "bf16_depth", "bf16_win", "bf16_nw",
+            "v2_ranges_per_cu", "conv_nt", "conv_strip"]
+    removed = ["spconv_bf16_v1", "v2_depth", "v2_tm", "v2_ldspad", "v2_uniform", "v2_rowcost", "strict"]
+    assert len(kept) == 13 and len(removed) == 7
+    header = open(os.path.join(REPO, "include", "futuredet_hip.h")).read()
+    for name in kept:
+        assert L.fd_tuning_set(name.encode(), 0) == 0, name
+        assert '"%s"' % name in header, name
+    for name in removed + ["no_such_knob"]:
+        assert L.fd_tuning_set(name.encode(), 0) == -1, name  # FD_EINVAL
+        assert name.encode() in L.fd_last_error(), name
+
+
 def test_collate_prefixes_batch_index():
     from futuredet_amd.collate import collate_kitti_multi
 

@@ -5,8 +5,7 @@
 out=gpurun_out/r5ev; mkdir -p $out
 nf() { grep -v amdgpu.ids; }
 { echo "# python tools/spconv_bench.py --dtype bf16 --levels 1,2,3 --win 0,-1   (win=0: LDS-window kernel where it applies, -1: RING / RESIDENT kernels)";
-  python tools/spconv_bench.py --dtype bf16 --levels 1,2,3 --win 0,-1 2>&1 | nf;
-  echo "# four-wave window shapes (bf16_nw = 4), row groups 1..4"; python tools/spconv_bench.py --dtype bf16 --levels 2,3 --win 0 --exp 4 --rg 1,2,3,4 2>&1 | nf; } > $out/bf16win_bench.txt
+  python tools/spconv_bench.py --dtype bf16 --levels 1,2,3 --win 0,-1 2>&1 | nf; } > $out/bf16win_bench.txt
 { echo "# FD_LIB_PATH=tools/probes/libfd_fd_spconv_bf16win_trace.so python tools/bf16win_trace.py 0   (tuning build -DFD_WIN_TRACE: ~25 % slower than the product)";
   FD_LIB_PATH=tools/probes/libfd_fd_spconv_bf16win_trace.so python tools/bf16win_trace.py 0 2>&1 | nf; } > $out/bf16win_phase_trace.txt
 python tools/window_stats.py 2>&1 | nf > $out/window_stats.txt

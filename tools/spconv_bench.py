@@ -19,12 +19,8 @@ ap.add_argument("--points", type=int, default=300000)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--modes", default="tiles,uniform,balanced")
 ap.add_argument("--rpc", default="0")
-ap.add_argument("--tm", type=int, default=0, help="chunk rows override (64 | 128)")
-ap.add_argument("--depth", type=int, default=0)
-ap.add_argument("--ldspad", type=int, default=0, help="extra LDS bytes per workgroup (occupancy experiments; 1 = drop the 64->64 floor)")
 ap.add_argument("--gp", default="0", help="bf16: comma list of bf16_gp knob values (0 = gather-pipeline kernel, -1 = the older kernels)")
 ap.add_argument("--rg", default="0", help="bf16 gather pipeline: comma list of row groups per wave (0 = heuristic)")
-ap.add_argument("--exp", type=int, default=0, help="bf16: experiment knob (timing only, results wrong)")
 ap.add_argument("--bdepth", default="0", help="bf16 gather pipeline: comma list of ring depths (0 = heuristic)")
 ap.add_argument("--win", default="0", help="bf16: comma list of bf16_win knob values (0 = LDS-window kernel where it applies, -1 = RING / RESIDENT kernels)")
 args = ap.parse_args()
@@ -39,10 +35,6 @@ bb.load_state_dict(seeded_state_dict(bb, 7), strict=False)
 bb = bb.to(dev).eval()
 idx = bb.build_indexes(lambda i0: i0.mark(out["coors"][:m].contiguous()), 1, [1440, 1440, 40], dev)
 MODE = {"tiles": "tiles", "uniform": False, "balanced": True}
-hip_ops.set_tuning("v2_tm", args.tm)
-hip_ops.set_tuning("v2_depth", args.depth)
-hip_ops.set_tuning("v2_ldspad", args.ldspad)
-hip_ops.set_tuning("bf16_nw", args.exp)
 for lvl in [int(v) for v in args.levels.split(",")]:
     C = [16, 32, 64, 128][lvl]
     ix = idx[lvl]
@@ -77,7 +69,7 @@ for lvl in [int(v) for v in args.levels.split(",")]:
             key = (gp, wn)
             if key not in ref:
                 ref[key] = y.clone()
-                for other in ([] if args.exp else ref.values()):  # two bf16 kernel families: same data, different summation trees
+                for other in ref.values():  # two bf16 kernel families: same data, different summation trees
                     assert float((other.float() - y.float()).abs().max()) <= 2e-2 * float(other.float().abs().max()), "bf16 kernels disagree"
             assert torch.equal(ref[key], y), "work distribution changed the result"
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,6 +1,6 @@
 """Micro-benchmark of the three strided sparse convolutions (16 -> 32, 32 -> 64, 64 -> 128; scn.py:110,120,130) on the real rulebooks of
-synthetic clouds: pairs, fill statistics of the rulebook and the launch time per tuning variant.
-usage: python tools/spconv_down_bench.py [--dtype fp32|bf16] [--batch 1] [--depth 0,2,3,4] [--tm 0,64,128]"""
+synthetic clouds: pairs, fill statistics of the rulebook and the launch time.
+usage: python tools/spconv_down_bench.py [--dtype fp32|bf16] [--batch 1]"""
 import argparse
 import os
 import sys
@@ -15,8 +15,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--dtype", default="fp32")
 ap.add_argument("--batch", type=int, default=1)
 ap.add_argument("--iters", type=int, default=20)
-ap.add_argument("--depth", default="0")
-ap.add_argument("--tm", default="0")
 args = ap.parse_args()
 dev = torch.device("cuda")
 dt = torch.float32 if args.dtype == "fp32" else torch.bfloat16
@@ -47,21 +45,15 @@ for lvl in (0, 1, 2):
     bias = torch.zeros(cout, device=dev)
     print("level %d -> %d: %d -> %d channels, %d input rows, %d output rows, %d pairs (%.1f per output row, fill %.2f of the (row, tap) slots; "
           "%.2f of the (16-row, tap) items hold a pair)" % (lvl, lvl + 1, cin, cout, src.n, n, pairs, pairs / n, pairs / (27.0 * n), items16), flush=True)
-    for depth in [int(t) for t in args.depth.split(",")]:
-        for tm in [int(t) for t in args.tm.split(",")]:
-            hip_ops.set_tuning("v2_depth", depth)
-            hip_ops.set_tuning("v2_tm", tm)
-            f = lambda: hip_ops.spconv_apply(x, wpk, bias, nbr, n, cout, relu=True)  # noqa: E731
-            for _ in range(3):
-                f()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                f()
-            e1.record()
-            torch.cuda.synchronize()
-            us = 1e3 * e0.elapsed_time(e1) / args.iters
-            print("   %s depth=%d tm=%d: %.1f us, %.1f TFLOP/s by pairs" % (args.dtype, depth, tm, us, 2.0 * pairs * cin * cout / us * 1e-6), flush=True)
-hip_ops.set_tuning("v2_depth", 0)
-hip_ops.set_tuning("v2_tm", 0)
+    f = lambda: hip_ops.spconv_apply(x, wpk, bias, nbr, n, cout, relu=True)  # noqa: E731
+    for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.iters):
+        f()
+    e1.record()
+    torch.cuda.synchronize()
+    us = 1e3 * e0.elapsed_time(e1) / args.iters
+    print("   %s: %.1f us, %.1f TFLOP/s by pairs" % (args.dtype, us, 2.0 * pairs * cin * cout / us * 1e-6), flush=True)
