@@ -4,7 +4,8 @@ Module / parameter names reproduce the reference so checkpoints load unchanged
 (conv_input.0.weight [3,3,3,5,16], conv1.0.conv1.{weight,bias}, conv1.0.bn1.*, conv2.0.weight, ...).
 Two execution paths, both on the HIP kernels:
   * generic: the spconv-surface modules one by one (SparseSequential / SparseBasicBlock.forward), used in
-    training mode or when a caller drives sub-modules directly;
+    training mode or when a caller drives sub-modules directly; ``train_dtype = torch.bfloat16`` runs it with bf16 rows
+    (mixed precision: fp32 parameters, gradients and BatchNorm statistics);
   * fused (eval): all five sparse indexes are built first (one host read of the five active counts), every
     conv runs as one fd_spconv_apply launch with BatchNorm1d folded into weight/bias and ReLU / residual
     fused in the epilogue, features stay channel-padded and in index order, then fd_densify.
@@ -89,6 +90,8 @@ class SpMiddleResNetFHD(nn.Module):
         self.dense_dtype = None              # dtype of the BEV map handed to the neck (default: compute dtype)
         self.profile_hook = None             # callable(tag, algorithmic_bytes, flops, fn) used by bench.py
         self.fused_bn = False                # training: BatchNorm1d (+ residual) + ReLU on the fused kernels (sparse.batch_norm_act)
+        self.train_dtype = torch.float32     # training: dtype of the feature rows; torch.bfloat16 = mixed precision (fp32 parameters,
+                                             # gradients and BatchNorm statistics).  compute_dtype keeps meaning the eval path
 
     # ------------------------------------------------------------------------------------------------ generic
     def _bn_act(self, features, bn, relu, residual=None):
@@ -96,6 +99,11 @@ class SpMiddleResNetFHD(nn.Module):
         call them (CPU, double, eval, no_grad, affine=False, track_running_stats=False, momentum=None, fewer than 2 rows)."""
         if spconv.batch_norm_fusable(features, bn):
             return spconv.batch_norm_act(features, bn, residual=residual, relu=True)
+        if features.dtype == torch.bfloat16:  # mixed precision: normalise, add and rectify in fp32 (fp32 batch and running statistics), one rounding
+            out = bn(features.float())
+            if residual is not None:
+                out = out + residual.float()
+            return spconv.relu_to_bf16(out)  # (saves the bf16 rows only: 6 bytes per element and layer stay alive for backward, against fp32's 8)
         out = bn(features)
         if residual is not None:
             out = out + residual
@@ -124,7 +132,10 @@ class SpMiddleResNetFHD(nn.Module):
         sparse_shape = np.array(input_shape[::-1]) + [1, 0, 0]  # scn.py:151
         ret = spconv.SparseConvTensor(voxel_features, coors.int(), sparse_shape, batch_size)
         stages = (self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.extra_conv)
-        if self.fused_bn and self.training and torch.is_grad_enabled():
+        mixed = self.train_dtype == torch.bfloat16 and self.training and torch.is_grad_enabled()
+        if mixed:  # the rows are bf16 from here to the BEV map; every stage through _run_stage, whose _bn_act normalises them in fp32
+            ret.features = ret.features.to(torch.bfloat16)
+        if mixed or (self.fused_bn and self.training and torch.is_grad_enabled()):
             run = [lambda x, seq=seq: self._run_stage(seq, x) for seq in stages]
         else:
             run = stages
@@ -134,6 +145,8 @@ class SpMiddleResNetFHD(nn.Module):
         x_conv3 = run[3](x_conv2)
         x_conv4 = run[4](x_conv3)
         ret = run[5](x_conv4).dense()
+        if mixed:
+            ret = ret.float()  # the neck trains in fp32
         N, C, D, H, W = ret.shape
         ret = ret.view(N, C * D, H, W)
         return ret, {"conv1": x_conv1, "conv2": x_conv2, "conv3": x_conv3, "conv4": x_conv4}
@@ -245,9 +258,12 @@ class SpMiddleResNetFHD(nn.Module):
 
     def forward(self, voxel_features, coors, batch_size, input_shape):
         if self.training:
-            if self.compute_dtype != torch.float32 and torch.is_grad_enabled():
-                raise NotImplementedError("SpMiddleResNetFHD: training runs the fp32 sparse convolution only; the %s path is inference-only "
-                                          "(set compute_dtype = torch.float32 to train)" % self.compute_dtype)
+            if self.train_dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError("SpMiddleResNetFHD: train_dtype must be torch.float32 or torch.bfloat16 (got %s)" % (self.train_dtype,))
+            if self.train_dtype == torch.float32 and self.compute_dtype != torch.float32 and torch.is_grad_enabled():
+                raise NotImplementedError("SpMiddleResNetFHD: with train_dtype = torch.float32 training runs the fp32 sparse convolution only; "
+                                          "compute_dtype = %s selects the inference path (set train_dtype = torch.bfloat16 for mixed-precision "
+                                          "training, or compute_dtype = torch.float32)" % self.compute_dtype)
             return self.forward_generic(voxel_features, coors, batch_size, input_shape)
         coors = coors.int().contiguous()
         dev = voxel_features.device

@@ -71,6 +71,11 @@ int spconv_bf16_win_dispatch(const SpconvCall &c);     // fd_spconv_bf16win.hip:
 int spconv_bf16_ws_dispatch(const SpconvCall &c);      // fd_spconv_bf16.hip: RESIDENT / RING kernels
 // fd_spconv_bf16win.hip: writes the win section
 void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*tobf)(float), uint16_t *dst);
+// Output rows per workgroup and per partial of the weight gradients (fd_spconv_grad.hip, fd_spconv_grad_bf16.hip): part of the summation
+// order, not a tuning knob; the shared second kernel derives the number of used chunks from it
+constexpr int kSpconvWgradChunk = 512;
+// fd_spconv_grad.hip: the second kernel of the weight gradients -- dw[k][e] = the tap's per-chunk partials [K][n_chunks][cc], summed in chunk order
+void spconv_wgrad_reduce(const float *partial, int K, int cc, int n_out, const int *n_out_dev, int n_chunks, float *dw, hipStream_t stream);
 
 // fd_conv2d_wino_pc.hip: 0 = launched, 1 = shape not supported by the variant, -1 = dynamic LDS refused; wide_items: work items of 128
 // output channels (tile 8) instead of 64 (tile 7)

@@ -421,12 +421,19 @@ bool launch_resident(const fd::SpconvCall &a, int rg, int depth) {
     return depth >= 4 ? WsKernel<CIN, COUT, 1, 4, 16, false>::launch(a) : WsKernel<CIN, COUT, 1, 2, 16, false>::launch(a);
 }
 
+// 64 -> 32, the input gradient of the strided 32 -> 64: RESIDENT with the same 108 KB of weights at K = 27 as 32 -> 64 and two 32-channel
+// chunks per gathered row, so the 8-wave workgroups (256 registers per lane) for every K.  Two row groups per wave fit the CU's 160 KB
+// next to the weights of up to 25 taps (4 KB per tap + 57 KB of rulebook slices); at K = 27 one row group runs (29 KB of slices).
+bool launch_resident_64_32(const fd::SpconvCall &a, int rg) {
+    return rg >= 2 ? WsKernel<64, 32, 2, 2, 8, false>::launch(a) : WsKernel<64, 32, 1, 4, 8, false>::launch(a);
+}
+
 // RING shapes (W[tap] double-buffered in LDS, 8 waves per workgroup, one barrier per tap).  rg = 0: the smallest number of
 // row groups per wave with which the resident workgroups cover the level in ONE pass (a second, partly empty pass would cost
 // a whole walk over the taps), else the largest.
 template <int CIN, int COUT>
 bool launch_ring(const fd::SpconvCall &a, int rg, int depth) {
-    constexpr int kMaxRG = COUT > 64 ? 2 : 4;  // (128 output columns: 3 row groups spill)
+    constexpr int kMaxRG = (COUT > 64 || CIN > 64) ? 2 : 4;  // (128 output columns: 3 row groups spill; 128 input channels: four chunks per gathered row)
     if (rg <= 0) {
         const int64_t n = a.n_expected;
         if (WsKernel<CIN, COUT, 1, 2, 8, true>::rows_per_round(a.K) >= n) rg = 1;
@@ -470,6 +477,13 @@ int spconv_bf16_ws_dispatch(const SpconvCall &a) {
             if (fd::tuning(fd::kTuneBf16RG) <= 0) rg = 2;  // (8-wave workgroups: 32 rows per wave keep 256 rows per workgroup pass)
             for (; rg >= 1 && !(ok = launch_resident<32, 64>(a, rg, depth)); rg >>= 1) {}
             break;
+        // the transposed shapes of the strided layers (their input gradient, fd_spconv_grad_bf16.hip)
+        case 32016: for (; rg >= 1 && !(ok = launch_resident<32, 16>(a, rg, depth)); rg >>= 1) {} break;
+        case 64032:
+            if (fd::tuning(fd::kTuneBf16RG) <= 0) rg = a.K > 25 ? 1 : 2;  // (see launch_resident_64_32)
+            for (; rg >= 1 && !(ok = launch_resident_64_32(a, rg)); rg >>= 1) {}
+            break;
+        case 128064: ok = launch_ring<128, 64>(a, rg, depth); break;
         case 64064: ok = launch_ring<64, 64>(a, rg, depth); break;
         case 64128: ok = launch_ring<64, 128>(a, rg, depth); break;
         case 128128: ok = launch_ring<128, 128>(a, rg, depth); break;

@@ -25,7 +25,7 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxTaps = 27;
-constexpr int kChunk = 512;  // output rows per workgroup (and per partial): part of the summation order, not a tuning knob
+constexpr int kChunk = fd::kSpconvWgradChunk;  // output rows per workgroup (and per partial): part of the summation order, not a tuning knob
 constexpr int kBatch = 32;   // pairs staged per LDS round (8 MFMA k-steps)
 constexpr int kPadF = 16;    // LDS row padding in floats: the four 16-lane groups of a read land on different bank sets
 
@@ -240,6 +240,12 @@ inline bool ok_channels(int c) { return c == 16 || c == 32 || c == 64 || c == 12
 
 }  // namespace
 
+namespace fd {
+void spconv_wgrad_reduce(const float *partial, int K, int cc, int n_out, const int *n_out_dev, int n_chunks, float *dw, hipStream_t stream) {
+    hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)(((int64_t)K * cc + 255) / 256)), dim3(256), 0, stream, partial, K, cc, n_out, n_out_dev, n_chunks, dw);
+}
+}  // namespace fd
+
 extern "C" size_t fd_spconv_wgrad_workspace_bytes(int K, int64_t n_out, int cin, int cout) {
     if (K <= 0 || n_out < 0 || cin <= 0 || cout <= 0) return 0;
     return (size_t)K * (size_t)((n_out + kChunk - 1) / kChunk) * cin * cout * sizeof(float);
@@ -270,7 +276,7 @@ extern "C" int fd_spconv_wgrad(const float *in_feats, int64_t n_in, const float 
         default: break;
     }
 #undef FD_W
-    hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((K * cc + 255) / 256)), dim3(256), 0, stream, partial, K, (int)cc, (int)n_out, n_out_dev, n_chunks, dw);
+    fd::spconv_wgrad_reduce(partial, K, (int)cc, (int)n_out, n_out_dev, n_chunks, dw, stream);
     return fd::check_launch("fd_spconv_wgrad");
 }
 

@@ -371,30 +371,43 @@ def pack_spconv_weight(w_kio, dtype=torch.float32):
 PACK_PLAIN, PACK_TRANSPOSED, PACK_FLIPPED_TRANSPOSED = 0, 1, 2  # fd_spconv_pack_weight_device modes: W[k], W[k]^T, W[K-1-k]^T
 
 
-def pack_spconv_weight_device(w_kio, mode=PACK_PLAIN):
-    """[K, Cin, Cout] float32 on the device -> fp32 fragment-ordered weights (fd_spconv_pack_weight byte for byte) of W[k], or, for
+def pack_spconv_weight_device(w_kio, mode=PACK_PLAIN, dtype=torch.float32):
+    """[K, Cin, Cout] float32 on the device -> fragment-ordered weights of ``dtype`` (fd_spconv_pack_weight byte for byte) of W[k], or, for
     the input gradient, of W[k]^T / W[K-1-k]^T (a Cout -> Cin problem).  No host round trip."""
     L = _lib.load()
+    if dtype not in _DT:
+        raise FutureDetHipError("pack_spconv_weight_device: dtype must be float32 or bfloat16 (got %s)" % (dtype,))
     w = _dev(w_kio.detach(), "w_kio", torch.float32)
     K, cin, cout = w.shape
     ci, co = (cout, cin) if mode else (cin, cout)
-    out = torch.empty((L.fd_spconv_packed_weight_bytes(K, ci, co, 0),), dtype=torch.uint8, device=w.device)
-    check(L.fd_spconv_pack_weight_device(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device")
+    out = torch.empty((L.fd_spconv_packed_weight_bytes(K, ci, co, _DT[dtype]),), dtype=torch.uint8, device=w.device)
+    if dtype == torch.float32:
+        check(L.fd_spconv_pack_weight_device(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device")
+    else:
+        check(L.fd_spconv_pack_weight_device_bf16(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device_bf16")
     return out
 
 
 def spconv_wgrad(feats, dy, nbr, n_out):
-    """dW[k] = sum_o feats[nbr[k][o]]^T dy[o] -> [K, Cin, Cout] float32 (deterministic, fd_spconv_wgrad)."""
+    """dW[k] = sum_o feats[nbr[k][o]]^T dy[o] -> [K, Cin, Cout] float32 (deterministic; fd_spconv_wgrad for float32 rows,
+    fd_spconv_wgrad_bf16 for bfloat16 rows -- feats and dy in the same one of the two)."""
     L = _lib.load()
-    feats = _dev(feats, "feats", torch.float32)
-    dy = _dev(dy, "dy", torch.float32)
+    if feats.dtype != dy.dtype or feats.dtype not in _DT:
+        raise FutureDetHipError("spconv_wgrad: feats and dy must both be float32 or both bfloat16 (got %s and %s)" % (feats.dtype, dy.dtype))
+    feats = _dev(feats, "feats")
+    dy = _dev(dy, "dy")
     K, nstride = nbr.shape
     cin, cout = feats.shape[1], dy.shape[1]
     assert dy.shape[0] >= n_out
     dw = torch.empty((K, cin, cout), dtype=torch.float32, device=feats.device)
-    ws = workspace.get("spconv_wgrad", L.fd_spconv_wgrad_workspace_bytes(K, n_out, cin, cout), feats.device)
-    check(L.fd_spconv_wgrad(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
-                            _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad")
+    if feats.dtype == torch.float32:
+        ws = workspace.get("spconv_wgrad", L.fd_spconv_wgrad_workspace_bytes(K, n_out, cin, cout), feats.device)
+        check(L.fd_spconv_wgrad(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
+                                _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad")
+    else:
+        ws = workspace.get("spconv_wgrad_bf16", L.fd_spconv_wgrad_bf16_workspace_bytes(K, n_out, cin, cout), feats.device)
+        check(L.fd_spconv_wgrad_bf16(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
+                                     _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad_bf16")
     return dw
 
 

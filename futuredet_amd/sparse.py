@@ -105,24 +105,48 @@ class _Densify(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feats, index):
-        ctx.index = index
+        ctx.index, ctx.dtype = index, feats.dtype
         return hip_ops.densify(feats, index)
 
     @staticmethod
     def backward(ctx, grad):
-        return hip_ops.dense_gather(grad.float(), ctx.index, grad.shape[1] // ctx.index.D), None
+        g = hip_ops.dense_gather(grad.float(), ctx.index, grad.shape[1] // ctx.index.D)
+        return (g if ctx.dtype == torch.float32 else g.to(ctx.dtype)), None
+
+
+class _ReluToBf16(torch.autograd.Function):
+    """relu(x).to(bfloat16) of an fp32 x in one node that saves only its bf16 output -- the tensor the next convolution saves anyway -- where
+    the two torch ops would keep the fp32 ReLU output as well.  The mask is y > 0: a positive fp32 value rounds to a positive bf16 value
+    (the formats share the exponent range; only values below 2^-134 vanish, and they carry no gradient worth the name)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.relu(x).to(torch.bfloat16)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return dy.float() * (y > 0)
+
+
+def relu_to_bf16(x):
+    return _ReluToBf16.apply(x)
 
 
 class _SparseConvFunction(torch.autograd.Function):
-    """One fp32 sparse convolution on channel-padded tensors: feats [n_in, cin_p], weight [K, cin_p, cout_p], bias [cout_p] or None.
+    """One sparse convolution on channel-padded tensors: feats [n_in, cin_p] fp32 or bf16, weight [K, cin_p, cout_p] and bias [cout_p] (or
+    None) always fp32 -- bf16 rows are mixed precision: fp32 master weights packed to bf16 on the device, fp32 accumulation, the fp32 bias
+    added before the one rounding of the output, bf16 dX, fp32 dW and dBias.
 
     forward:  fd_spconv_apply with device-packed weights (no BN folding, no fused ReLU / residual);
     backward: dX on fd_spconv_apply again (SubM: the same table with W[K-1-k]^T; strided: the transposed table with W[k]^T),
-              dW on fd_spconv_wgrad, dBias = sum of dY.  Saves the inputs only (an in-place ReLU follows the output)."""
+              dW on fd_spconv_wgrad / fd_spconv_wgrad_bf16, dBias = sum of dY.  Saves the inputs only (an in-place ReLU follows the output)."""
 
     @staticmethod
     def forward(ctx, feats, weight, bias, nbr, n_out, subm):
-        wpk = hip_ops.pack_spconv_weight_device(weight)
+        wpk = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_PLAIN, feats.dtype)
         out = hip_ops.spconv_apply(feats, wpk, bias, nbr, n_out, weight.shape[2])
         ctx.save_for_backward(feats, weight)
         ctx.nbr, ctx.n_out, ctx.subm, ctx.has_bias = nbr, n_out, subm, bias is not None
@@ -133,22 +157,23 @@ class _SparseConvFunction(torch.autograd.Function):
         feats, weight = ctx.saved_tensors
         nbr, n_out = ctx.nbr, ctx.n_out
         n_in, cin_p = feats.shape
-        dy = dy.float().contiguous()
+        dt = feats.dtype
+        dy = dy.to(dt).contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             if ctx.subm:  # the SubM table is symmetric: nbr[k][o] = i <=> nbr[K-1-k][i] = o
-                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_FLIPPED_TRANSPOSED)
+                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_FLIPPED_TRANSPOSED, dt)
                 dx = hip_ops.spconv_apply(dy, wt, None, nbr, n_in, cin_p)
             else:
                 inv = getattr(nbr, "inv", None)  # cached with the rulebook (indice_key)
                 if inv is None:
                     inv = nbr.inv = hip_ops.rulebook_transpose(nbr, n_out, n_in)
-                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_TRANSPOSED)
+                wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_TRANSPOSED, dt)
                 dx = hip_ops.spconv_apply(dy, wt, None, inv, n_in, cin_p)
         if ctx.needs_input_grad[1]:
             dw = hip_ops.spconv_wgrad(feats, dy, nbr, n_out)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy[:n_out].sum(0)
+            db = dy[:n_out].sum(0) if dt == torch.float32 else dy[:n_out].float().sum(0)
         return dx, dw, db, None, None, None
 
 
@@ -286,8 +311,10 @@ class SparseConvolution(SparseModule):
         params = [self.weight] + ([self.bias] if self.bias is not None else [])
         if torch.is_grad_enabled() and (x.features.requires_grad or (self.training and any(p.requires_grad for p in params))):
             return self._forward_autograd(x, out_index, nbr)
-        wpk, bias, cin_p, cout_p = self.packed_weight(torch.float32)
         feats = x.features
+        if feats.dtype not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError("sparse convolution takes fp32 or bf16 features (features are %s)" % feats.dtype)
+        wpk, bias, cin_p, cout_p = self.packed_weight(feats.dtype)  # the kernel's dtype is the rows': bf16 rows meet a frozen convolution in mixed-precision training
         if feats.shape[1] != cin_p:
             feats = torch.nn.functional.pad(feats, (0, cin_p - feats.shape[1]))
         out = hip_ops.spconv_apply(feats.contiguous(), wpk, bias, nbr, out_index.n, cout_p)
@@ -299,9 +326,10 @@ class SparseConvolution(SparseModule):
 
 
     def _forward_autograd(self, x, out_index, nbr):
-        """The differentiable path (fp32): padding and slicing are torch ops around _SparseConvFunction."""
-        if x.features.dtype != torch.float32:
-            raise NotImplementedError("sparse convolution training is fp32 only (features are %s)" % x.features.dtype)
+        """The differentiable path (fp32 rows, or bf16 rows with fp32 parameters): padding and slicing are torch ops around
+        _SparseConvFunction."""
+        if x.features.dtype not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError("sparse convolution training takes fp32 or bf16 features (features are %s)" % x.features.dtype)
         K = int(np.prod(self.kernel_size))
         cin_p, cout_p = pad_channels(self.in_channels), pad_channels(self.out_channels)
         F = torch.nn.functional

@@ -505,6 +505,26 @@ int fd_dense_gather(const float *dense, int64_t stride_b, int64_t stride_c, int6
                     int64_t n_rows, const int32_t *n_dev, int c, float *feats, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Mixed-precision training of the sparse convolution (fd_spconv_grad_bf16.hip): bf16 rows, fp32 master weights and gradients.
+ * Purely additive: fd_abi_version() stays 8.  The forward is fd_spconv_apply(dtype 1); the input gradient is fd_spconv_apply(dtype 1)
+ * on the transposed problem exactly as above, for which the bf16 kernels also take 32 -> 16, 64 -> 32 and 128 -> 64.
+ *   fd_spconv_wgrad_bf16:  fd_spconv_wgrad with bf16 in_feats [n_in, cin] and dy [n_out, cout]; dw [K, cin, cout] stays FP32 (overwritten).
+ *                     bf16 x bf16 products accumulated in fp32 on the matrix core.  (cin, cout) in {16->16, 16->32, 32->32, 32->64, 64->64,
+ *                     64->128, 128->128}.  The same per-(512-row chunk, tap) partials in `workspace`
+ *                     (fd_spconv_wgrad_bf16_workspace_bytes; 0 = bad sizes), summed in chunk order: bit-identical whatever the launch, no
+ *                     atomics.  n_out_dev as in fd_spconv_apply; n_out == 0 writes zeros.  Feature matrices of 2 GB and more: FD_EINVAL.
+ *                     Neither allocates nor synchronises.
+ *   fd_spconv_pack_weight_device_bf16: fd_spconv_pack_weight (dtype 1) on the device, byte for byte (every section of the buffer, the same
+ *                     round-to-nearest-even), of W'[k] = W[k] (mode 0), W[k]^T (mode 1: a [K, cout, cin] problem) or W[K-1-k]^T (mode 2);
+ *                     w_kio [K, cin, cout] fp32 device memory, wpacked fd_spconv_packed_weight_bytes(K, cin', cout', 1) bytes.  One launch,
+ *                     no host round trip.
+ * ------------------------------------------------------------------------------------------------- */
+size_t fd_spconv_wgrad_bf16_workspace_bytes(int K, int64_t n_out, int cin, int cout);
+int fd_spconv_wgrad_bf16(const void *in_feats, int64_t n_in, const void *dy, const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out,
+                         const int32_t *n_out_dev, int cin, int cout, float *dw, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_spconv_pack_weight_device_bf16(const float *w_kio, int K, int cin, int cout, int mode, void *wpacked, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training targets: AssignLabel's heat maps and box rows (fd_targets.hip) -- det3d/datasets/pipelines/preprocess.py:336-910
  * (NuScenesDataset branch) with gaussian_radius / draw_umich_gaussian of det3d/core/utils/center_utils.py:17-64, for a whole batch
  * [B, T] and every target set in two launches.  Purely additive: fd_abi_version() stays 8.
