@@ -89,15 +89,18 @@ class SpMiddleResNetFHD(nn.Module):
         self.dense_channels_last = True
         self.dense_dtype = None              # dtype of the BEV map handed to the neck (default: compute dtype)
         self.profile_hook = None             # callable(tag, algorithmic_bytes, flops, fn) used by bench.py
-        self.fused_bn = False                # training: BatchNorm1d (+ residual) + ReLU on the fused kernels (sparse.batch_norm_act)
+        self.fused_bn = False                # training: BatchNorm1d (+ residual) + ReLU on the fused kernels (sparse.batch_norm_act),
+                                             # on fp32 rows and on the bf16 rows of train_dtype = torch.bfloat16
         self.train_dtype = torch.float32     # training: dtype of the feature rows; torch.bfloat16 = mixed precision (fp32 parameters,
                                              # gradients and BatchNorm statistics).  compute_dtype keeps meaning the eval path
 
     # ------------------------------------------------------------------------------------------------ generic
     def _bn_act(self, features, bn, relu, residual=None):
-        """relu(bn(features) [+ residual]): the fused kernels where they apply, else the modules as SparseSequential / SparseBasicBlock
-        call them (CPU, double, eval, no_grad, affine=False, track_running_stats=False, momentum=None, fewer than 2 rows)."""
-        if spconv.batch_norm_fusable(features, bn):
+        """relu(bn(features) [+ residual]): with fused_bn the fused kernels where they apply (fp32 rows, and the bf16 rows of mixed
+        precision), else the modules as SparseSequential / SparseBasicBlock call them (CPU, double, eval, no_grad, affine=False,
+        track_running_stats=False, momentum=None, fewer than 2 rows).  Without fused_bn the modules always: mixed precision reaches
+        this method with the switch off."""
+        if self.fused_bn and spconv.batch_norm_fusable(features, bn):
             return spconv.batch_norm_act(features, bn, residual=residual, relu=True)
         if features.dtype == torch.bfloat16:  # mixed precision: normalise, add and rectify in fp32 (fp32 batch and running statistics), one rounding
             out = bn(features.float())
@@ -133,7 +136,7 @@ class SpMiddleResNetFHD(nn.Module):
         ret = spconv.SparseConvTensor(voxel_features, coors.int(), sparse_shape, batch_size)
         stages = (self.conv_input, self.conv1, self.conv2, self.conv3, self.conv4, self.extra_conv)
         mixed = self.train_dtype == torch.bfloat16 and self.training and torch.is_grad_enabled()
-        if mixed:  # the rows are bf16 from here to the BEV map; every stage through _run_stage, whose _bn_act normalises them in fp32
+        if mixed:  # the rows are bf16 from here to the BEV map; every stage through _run_stage, whose _bn_act normalises them with fp32 statistics
             ret.features = ret.features.to(torch.bfloat16)
         if mixed or (self.fused_bn and self.training and torch.is_grad_enabled()):
             run = [lambda x, seq=seq: self._run_stage(seq, x) for seq in stages]

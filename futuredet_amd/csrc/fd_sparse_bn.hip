@@ -1,4 +1,4 @@
-// Training-mode BatchNorm1d over the rows of a sparse feature matrix x [n, C] (fp32, row-major), fused with what follows it in
+// Training-mode BatchNorm1d over the rows of a sparse feature matrix x [n, C] (fp32 or bf16, row-major), fused with what follows it in
 // SpMiddleResNetFHD (det3d/models/backbones/scn.py:37-176): y = act(gamma (x - mean) invstd + beta [+ residual]), and its backward.
 //
 // Statistics.  Rows are cut into chunks of kChunk (= FD_SPARSE_BN_CHUNK) rows: chunk b owns rows [b kChunk, min((b + 1) kChunk, n)).
@@ -16,8 +16,13 @@
 // chunk, added per group in chunk order in double; pass 2: every workgroup re-sums the group partials in the same fixed order,
 // dx = gamma invstd (g - dbeta / n - x^ dgamma / n), d_residual = g.
 //
-// Thread layout of every pass: a row is C / 4 float4 columns; thread t takes column t % (C / 4) of rows t / (C / 4), + 256 / (C / 4), ...
-// (16-byte loads and stores, a wave reads whole rows).  Row lanes are added in lane order through LDS.
+// Thread layout of every pass: a row is C / 4 column quads; thread t takes quad t % (C / 4) of rows t / (C / 4), + 256 / (C / 4), ...
+// (a wave reads whole rows).  Row lanes are added in lane order through LDS.
+//
+// Row type.  Every kernel is a template over the type T of the row tensors (x, residual, y, dy, dx, d_residual): float, a quad is one
+// float4 (16 bytes), or bf16_t, a quad is one 8-byte group that ld4 widens exactly to fp32 and st4 rounds to nearest even.  Nothing else
+// differs: the bf16 form computes what the fp32 form computes on the widened rows, and rounds once.  Parameters, statistics, saved and the
+// workspace partials are fp32 either way.
 #include "fd_common.h"
 
 namespace {
@@ -37,8 +42,31 @@ inline int groups_cap(int64_t n) { return (int)(chunks_of(n) < kMaxGroups ? chun
 // rows per apply workgroup: a function of the capacity only (the apply pass is element-wise: its cut does not touch the sums)
 inline int apply_rows(int64_t n) { return (int)((chunks_of(n) + kMaxApplyBlocks - 1) / kMaxApplyBlocks) * kChunk; }
 
+typedef uint16_t bf16_t;  // the bits of a bfloat16
+
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+__device__ __forceinline__ float ld1(const float *p) { return *p; }
+
+// bf16 -> fp32 is exact: the 16 bits are the upper half of the fp32 pattern
+__device__ __forceinline__ float4 ld4(const bf16_t *p) {
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                       __uint_as_float(u.y & 0xffff0000u));
+}
+__device__ __forceinline__ float ld1(const bf16_t *p) { return __uint_as_float((unsigned)*p << 16); }
+// round to nearest even (fd_spconv_grad_bf16.hip's to_bf16_rne); a NaN stays a NaN instead of carrying into the sign
+__device__ __forceinline__ unsigned to_bf16_rne(float v) {
+    const unsigned u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ void st4(bf16_t *p, float4 v) {
+    uint2 u;
+    u.x = to_bf16_rne(v.x) | (to_bf16_rne(v.y) << 16);
+    u.y = to_bf16_rne(v.z) | (to_bf16_rne(v.w) << 16);
+    *reinterpret_cast<uint2 *>(p) = u;
+}
 
 // The cut of nv valid rows: chunks, chunks per group, groups.  Device side: everything follows from the valid row count.
 struct Cut {
@@ -65,7 +93,8 @@ __device__ __forceinline__ float lane_sum(float4 v, float *s_red, int rl, int q,
 }
 
 // ---- forward pass 1: part[g] = [mean_g[C], M2_g[C]]
-__global__ void __launch_bounds__(kThreads) bn_stats(const float *__restrict__ x, int n, const int *__restrict__ n_dev, int C,
+template <typename T>
+__global__ void __launch_bounds__(kThreads) bn_stats(const T *__restrict__ x, int n, const int *__restrict__ n_dev, int C,
                                                       float *__restrict__ part) {
     __shared__ __attribute__((aligned(16))) float red[kRedFloats];
     __shared__ __attribute__((aligned(16))) float s_mean[kMaxC];
@@ -94,7 +123,7 @@ __global__ void __launch_bounds__(kThreads) bn_stats(const float *__restrict__ x
         const float tot = lane_sum(s, red, rl, q, RL, C);
         const float nb = (float)(r1 - r0);
         float mb = 0.f;
-        if (threadIdx.x < C) s_mean[threadIdx.x] = mb = x[(int64_t)r0 * C + threadIdx.x] + tot / nb;
+        if (threadIdx.x < C) s_mean[threadIdx.x] = mb = ld1(x + (int64_t)r0 * C + threadIdx.x) + tot / nb;
         __syncthreads();
         const float4 m = ld4(&s_mean[4 * q]);
         s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -160,10 +189,11 @@ __device__ __forceinline__ double slice_total(const D4 &a, double *s_acc, const 
 }
 
 // ---- forward pass 2: statistics from the group partials, then y for the workgroup's rows
-__global__ void __launch_bounds__(kThreads) bn_apply(const float *__restrict__ x, const float *__restrict__ residual,
+template <typename T>
+__global__ void __launch_bounds__(kThreads) bn_apply(const T *__restrict__ x, const T *__restrict__ residual,
                                                       const float *__restrict__ gamma, const float *__restrict__ beta, int n,
                                                       const int *__restrict__ n_dev, int C, int relu, float eps, double momentum,
-                                                      int rows_per_block, const float *__restrict__ part, float *__restrict__ y,
+                                                      int rows_per_block, const float *__restrict__ part, T *__restrict__ y,
                                                       float *__restrict__ saved, float *__restrict__ running_mean,
                                                       float *__restrict__ running_var, long long *__restrict__ num_batches_tracked) {
     __shared__ double s_acc[kRedFloats];
@@ -255,7 +285,8 @@ __global__ void __launch_bounds__(kThreads) bn_apply(const float *__restrict__ x
     }
 }
 
-__device__ __forceinline__ float4 masked(const float *__restrict__ dy, const float *__restrict__ y, int relu, int64_t o) {
+template <typename T>
+__device__ __forceinline__ float4 masked(const T *__restrict__ dy, const T *__restrict__ y, int relu, int64_t o) {
     float4 g = ld4(dy + o);
     if (relu) {
         const float4 yv = ld4(y + o);
@@ -268,7 +299,8 @@ __device__ __forceinline__ float4 masked(const float *__restrict__ dy, const flo
 }
 
 // ---- backward pass 1: part[g] = [sum g [C], sum g x^ [C]]
-__global__ void __launch_bounds__(kThreads) bn_grad_sums(const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ y,
+template <typename T>
+__global__ void __launch_bounds__(kThreads) bn_grad_sums(const T *__restrict__ dy, const T *__restrict__ x, const T *__restrict__ y,
                                                           const float *__restrict__ saved, int n, const int *__restrict__ n_dev, int C,
                                                           int relu, float *__restrict__ part) {
     __shared__ __attribute__((aligned(16))) float red[kRedFloats];
@@ -310,10 +342,11 @@ __global__ void __launch_bounds__(kThreads) bn_grad_sums(const float *__restrict
 }
 
 // ---- backward pass 2: dbeta / dgamma from the group partials, then dx (and d_residual) for the workgroup's rows
-__global__ void __launch_bounds__(kThreads) bn_grad_apply(const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ y,
+template <typename T>
+__global__ void __launch_bounds__(kThreads) bn_grad_apply(const T *__restrict__ dy, const T *__restrict__ x, const T *__restrict__ y,
                                                            const float *__restrict__ gamma, const float *__restrict__ saved, int n,
                                                            const int *__restrict__ n_dev, int C, int relu, int rows_per_block,
-                                                           const float *__restrict__ part, float *__restrict__ dx, float *__restrict__ d_residual,
+                                                           const float *__restrict__ part, T *__restrict__ dx, T *__restrict__ d_residual,
                                                            float *__restrict__ dgamma, float *__restrict__ dbeta) {
     __shared__ double s_acc[kRedFloats];
     __shared__ __attribute__((aligned(16))) float s_mean[kMaxC];
@@ -398,41 +431,63 @@ extern "C" size_t fd_sparse_bn_workspace_bytes(int64_t n, int C) {
                fd_sparse_bn_workspace_bytes(n, C));                                                                                     \
     FD_REQUIRE(aligned16(workspace), fn ": the workspace must be 16-byte aligned")
 
+// The two entry points per row type share their bodies: fn is the name the messages carry, T the row type.
+#define FD_SBN_FORWARD(fn, T)                                                                                                          \
+    FD_REQUIRE(x && gamma && beta, fn ": null x, gamma or beta");                                                                      \
+    FD_REQUIRE(y && saved, fn ": null y or saved");                                                                                    \
+    FD_REQUIRE(running_mean && running_var && num_batches_tracked, fn ": null running statistics");                                    \
+    FD_SBN_CHECK(fn);                                                                                                                  \
+    FD_REQUIRE(eps > 0.f, fn ": eps must be > 0");                                                                                     \
+    FD_REQUIRE(momentum >= 0.0 && momentum <= 1.0, fn ": momentum must be in [0, 1]");                                                 \
+    FD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(saved) && (!residual || aligned16(residual)),                                 \
+               fn ": x, residual, y and saved must be 16-byte aligned");                                                               \
+    hipStream_t st = fd::as_stream(stream_);                                                                                           \
+    const int rows = apply_rows(n);                                                                                                    \
+    float *part = (float *)workspace;                                                                                                  \
+    hipLaunchKernelGGL(bn_stats<T>, dim3((unsigned)groups_cap(n)), dim3(kThreads), 0, st, x, (int)n, n_dev, C, part);                  \
+    hipLaunchKernelGGL(bn_apply<T>, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, st, x, residual, gamma, beta, (int)n,  \
+                       n_dev, C, relu, eps, momentum, rows, (const float *)part, y, saved, running_mean, running_var,                  \
+                       (long long *)num_batches_tracked);                                                                              \
+    return fd::check_launch(fn)
+
+#define FD_SBN_BACKWARD(fn, T)                                                                                                         \
+    FD_REQUIRE(dy && x && gamma && saved, fn ": null dy, x, gamma or saved");                                                          \
+    FD_REQUIRE(y || !relu, fn ": null y (the ReLU mask)");                                                                             \
+    FD_REQUIRE(dx && dgamma && dbeta, fn ": null dx, dgamma or dbeta");                                                                \
+    FD_SBN_CHECK(fn);                                                                                                                  \
+    FD_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(y) && aligned16(saved) && aligned16(dx) && aligned16(d_residual),            \
+               fn ": dy, x, y, saved, dx and d_residual must be 16-byte aligned");                                                     \
+    hipStream_t st = fd::as_stream(stream_);                                                                                           \
+    const int rows = apply_rows(n);                                                                                                    \
+    float *part = (float *)workspace;                                                                                                  \
+    hipLaunchKernelGGL(bn_grad_sums<T>, dim3((unsigned)groups_cap(n)), dim3(kThreads), 0, st, dy, x, y, saved, (int)n, n_dev, C, relu, \
+                       part);                                                                                                          \
+    hipLaunchKernelGGL(bn_grad_apply<T>, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, st, dy, x, y, gamma, saved,       \
+                       (int)n, n_dev, C, relu, rows, (const float *)part, dx, d_residual, dgamma, dbeta);                              \
+    return fd::check_launch(fn)
+
 extern "C" int fd_sparse_bn_train_forward(const float *x, const float *residual, const float *gamma, const float *beta, int64_t n,
                                           const int32_t *n_dev, int C, int relu, float eps, double momentum, float *y, float *saved,
                                           float *running_mean, float *running_var, int64_t *num_batches_tracked, void *workspace,
                                           size_t workspace_bytes, fd_stream_t stream_) {
-    FD_REQUIRE(x && gamma && beta, "fd_sparse_bn_train_forward: null x, gamma or beta");
-    FD_REQUIRE(y && saved, "fd_sparse_bn_train_forward: null y or saved");
-    FD_REQUIRE(running_mean && running_var && num_batches_tracked, "fd_sparse_bn_train_forward: null running statistics");
-    FD_SBN_CHECK("fd_sparse_bn_train_forward");
-    FD_REQUIRE(eps > 0.f, "fd_sparse_bn_train_forward: eps must be > 0");
-    FD_REQUIRE(momentum >= 0.0 && momentum <= 1.0, "fd_sparse_bn_train_forward: momentum must be in [0, 1]");
-    FD_REQUIRE(aligned16(x) && aligned16(y) && aligned16(saved) && (!residual || aligned16(residual)),
-               "fd_sparse_bn_train_forward: x, residual, y and saved must be 16-byte aligned");
-    hipStream_t st = fd::as_stream(stream_);
-    const int rows = apply_rows(n);
-    float *part = (float *)workspace;
-    hipLaunchKernelGGL(bn_stats, dim3((unsigned)groups_cap(n)), dim3(kThreads), 0, st, x, (int)n, n_dev, C, part);
-    hipLaunchKernelGGL(bn_apply, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, st, x, residual, gamma, beta, (int)n, n_dev, C, relu, eps,
-                       momentum, rows, (const float *)part, y, saved, running_mean, running_var, (long long *)num_batches_tracked);
-    return fd::check_launch("fd_sparse_bn_train_forward");
+    FD_SBN_FORWARD("fd_sparse_bn_train_forward", float);
+}
+
+extern "C" int fd_sparse_bn_train_forward_bf16(const uint16_t *x, const uint16_t *residual, const float *gamma, const float *beta, int64_t n,
+                                               const int32_t *n_dev, int C, int relu, float eps, double momentum, uint16_t *y, float *saved,
+                                               float *running_mean, float *running_var, int64_t *num_batches_tracked, void *workspace,
+                                               size_t workspace_bytes, fd_stream_t stream_) {
+    FD_SBN_FORWARD("fd_sparse_bn_train_forward_bf16", bf16_t);
 }
 
 extern "C" int fd_sparse_bn_train_backward(const float *dy, const float *x, const float *y, const float *gamma, const float *saved, int64_t n,
                                            const int32_t *n_dev, int C, int relu, float *dx, float *d_residual, float *dgamma, float *dbeta,
                                            void *workspace, size_t workspace_bytes, fd_stream_t stream_) {
-    FD_REQUIRE(dy && x && gamma && saved, "fd_sparse_bn_train_backward: null dy, x, gamma or saved");
-    FD_REQUIRE(y || !relu, "fd_sparse_bn_train_backward: null y (the ReLU mask)");
-    FD_REQUIRE(dx && dgamma && dbeta, "fd_sparse_bn_train_backward: null dx, dgamma or dbeta");
-    FD_SBN_CHECK("fd_sparse_bn_train_backward");
-    FD_REQUIRE(aligned16(dy) && aligned16(x) && aligned16(y) && aligned16(saved) && aligned16(dx) && aligned16(d_residual),
-               "fd_sparse_bn_train_backward: dy, x, y, saved, dx and d_residual must be 16-byte aligned");
-    hipStream_t st = fd::as_stream(stream_);
-    const int rows = apply_rows(n);
-    float *part = (float *)workspace;
-    hipLaunchKernelGGL(bn_grad_sums, dim3((unsigned)groups_cap(n)), dim3(kThreads), 0, st, dy, x, y, saved, (int)n, n_dev, C, relu, part);
-    hipLaunchKernelGGL(bn_grad_apply, dim3((unsigned)((n + rows - 1) / rows)), dim3(kThreads), 0, st, dy, x, y, gamma, saved, (int)n, n_dev, C, relu,
-                       rows, (const float *)part, dx, d_residual, dgamma, dbeta);
-    return fd::check_launch("fd_sparse_bn_train_backward");
+    FD_SBN_BACKWARD("fd_sparse_bn_train_backward", float);
+}
+
+extern "C" int fd_sparse_bn_train_backward_bf16(const uint16_t *dy, const uint16_t *x, const uint16_t *y, const float *gamma, const float *saved,
+                                                int64_t n, const int32_t *n_dev, int C, int relu, uint16_t *dx, uint16_t *d_residual,
+                                                float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, fd_stream_t stream_) {
+    FD_SBN_BACKWARD("fd_sparse_bn_train_backward_bf16", bf16_t);
 }

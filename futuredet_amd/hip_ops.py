@@ -1377,38 +1377,50 @@ def _sparse_bn_ws(L, n, c, device):
     return workspace.get("sparse_bn", L.fd_sparse_bn_workspace_bytes(int(n), int(c)), device)
 
 
+def _sparse_bn_rows(x, name):
+    """the row tensor that sets a call's row type: fp32 or bf16 -> (tensor, entry-point suffix)"""
+    x = _dev(x, name)
+    if x.dtype == torch.float32:
+        return x, ""
+    if x.dtype == torch.bfloat16:
+        return x, "_bf16"
+    raise FutureDetHipError("%s must be torch.float32 or torch.bfloat16, got %s" % (name, x.dtype))
+
+
 def sparse_bn_train_forward(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, residual=None, relu=True,
                             n_dev=None):
-    """fd_sparse_bn_train_forward: y = act(gamma (x - mean) invstd + beta [+ residual]) on batch statistics over the rows of x [n, C]
-    fp32; updates running_mean / running_var / num_batches_tracked in place on the device (their ``_version`` is NOT bumped: the
-    caller does that).  ``n_dev``: int32 [1] on the device, the valid row count (n = x.shape[0] is then the capacity).
+    """fd_sparse_bn_train_forward[_bf16]: y = act(gamma (x - mean) invstd + beta [+ residual]) on batch statistics over the rows of
+    x [n, C], fp32 or bf16 (``residual`` and the returned y have x's dtype; parameters, statistics and ``saved`` are always fp32); updates
+    running_mean / running_var / num_batches_tracked in place on the device (their ``_version`` is NOT bumped: the caller does that).
+    ``n_dev``: int32 [1] on the device, the valid row count (n = x.shape[0] is then the capacity).
     Returns (y, saved [2, C] = mean, invstd).  Two launches, nothing is synchronised."""
     L = _lib.load()
-    x = _dev(x, "x", torch.float32)
+    x, sfx = _sparse_bn_rows(x, "x")
     n, c = x.shape
     for t, name in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
         if _dev(t, name, torch.float32).numel() != c:
             raise FutureDetHipError("%s must hold %d channels, got %d" % (name, c, t.numel()))
     _dev(num_batches_tracked, "num_batches_tracked", torch.int64)
-    if residual is not None and _dev(residual, "residual", torch.float32).shape != x.shape:
+    if residual is not None and _dev(residual, "residual", x.dtype).shape != x.shape:
         raise FutureDetHipError("residual must be %s, got %s" % (tuple(x.shape), tuple(residual.shape)))
     out = torch.empty_like(x)
     saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
     ws = _sparse_bn_ws(L, n, c, x.device)
-    check(L.fd_sparse_bn_train_forward(_p(x), _p(residual), _p(gamma), _p(beta), n, _p(n_dev), c, int(bool(relu)), float(eps), float(momentum),
-                                       _p(out), _p(saved), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel(),
-                                       _stream()), "fd_sparse_bn_train_forward")
+    fn = "fd_sparse_bn_train_forward" + sfx
+    check(getattr(L, fn)(_p(x), _p(residual), _p(gamma), _p(beta), n, _p(n_dev), c, int(bool(relu)), float(eps), float(momentum), _p(out),
+                         _p(saved), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel(), _stream()), fn)
     return out, saved
 
 
 def sparse_bn_train_backward(dy, x, y, gamma, saved, relu=True, want_residual=False, n_dev=None):
-    """fd_sparse_bn_train_backward: -> (dx, d_residual or None, dgamma, dbeta).  ``y`` is the forward's output (the ReLU mask; may be
-    None with relu=False), ``saved`` what the forward returned."""
+    """fd_sparse_bn_train_backward[_bf16]: -> (dx, d_residual or None, dgamma, dbeta).  ``y`` is the forward's output (the ReLU mask; may
+    be None with relu=False), ``saved`` what the forward returned.  ``dy`` and ``y`` have x's dtype (fp32 or bf16), and so have dx and
+    d_residual; dgamma and dbeta are fp32."""
     L = _lib.load()
-    dy = _dev(dy, "dy", torch.float32)
-    x = _dev(x, "x", torch.float32)
+    x, sfx = _sparse_bn_rows(x, "x")
+    dy = _dev(dy, "dy", x.dtype)
     n, c = x.shape
-    if dy.shape != x.shape or (y is not None and _dev(y, "y", torch.float32).shape != x.shape):
+    if dy.shape != x.shape or (y is not None and _dev(y, "y", x.dtype).shape != x.shape):
         raise FutureDetHipError("dy and y must be %s" % (tuple(x.shape),))
     if _dev(saved, "saved", torch.float32).numel() != 2 * c or _dev(gamma, "gamma", torch.float32).numel() != c:
         raise FutureDetHipError("gamma / saved do not hold %d channels" % c)
@@ -1416,6 +1428,7 @@ def sparse_bn_train_backward(dy, x, y, gamma, saved, relu=True, want_residual=Fa
     dres = torch.empty_like(x) if want_residual else None
     dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
     ws = _sparse_bn_ws(L, n, c, x.device)
-    check(L.fd_sparse_bn_train_backward(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), n, _p(n_dev), c, int(bool(relu)), _p(dx), _p(dres),
-                                        _p(dgb[0]), _p(dgb[1]), _p(ws), ws.numel(), _stream()), "fd_sparse_bn_train_backward")
+    fn = "fd_sparse_bn_train_backward" + sfx
+    check(getattr(L, fn)(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), n, _p(n_dev), c, int(bool(relu)), _p(dx), _p(dres), _p(dgb[0]), _p(dgb[1]),
+                         _p(ws), ws.numel(), _stream()), fn)
     return dx, dres, dgb[0], dgb[1]

@@ -188,6 +188,9 @@ SIGNATURES = {
     "fd_sparse_bn_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+for _name in ("fd_sparse_bn_train_forward", "fd_sparse_bn_train_backward"):  # bf16 rows: the same argument lists
+    SIGNATURES[_name + "_bf16"] = SIGNATURES[_name]
+
 
 
 class FutureDetHipError(RuntimeError):

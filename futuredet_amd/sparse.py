@@ -180,7 +180,9 @@ class _SparseConvFunction(torch.autograd.Function):
 class _SparseBatchNormFunction(torch.autograd.Function):
     """Training-mode BatchNorm1d over the rows of x [n, C] fused with the residual add and ReLU that follow it (fd_sparse_bn.hip):
     y = act(gamma (x - mean) invstd + beta [+ residual]).  ``bn`` is the nn.BatchNorm1d module: the kernel updates its running
-    statistics and num_batches_tracked on the device.  Saves x and y: y is what the next convolution saves as its input."""
+    statistics and num_batches_tracked on the device.  Saves x and y: y is what the next convolution saves as its input.
+    x fp32 or bf16 (mixed precision): residual, y and every row gradient have x's dtype; gamma, beta, their gradients and the
+    statistics are fp32.  On bf16 rows no fp32 [n, C] tensor exists at any point."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, bn, relu):
@@ -198,16 +200,17 @@ class _SparseBatchNormFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, y, gamma, saved = ctx.saved_tensors
         want_res = ctx.needs_input_grad[3]
-        dx, dres, dgamma, dbeta = hip_ops.sparse_bn_train_backward(dy.float().contiguous(), x, y, gamma, saved, relu=ctx.relu,
+        dx, dres, dgamma, dbeta = hip_ops.sparse_bn_train_backward(dy.to(x.dtype).contiguous(), x, y, gamma, saved, relu=ctx.relu,
                                                                    want_residual=want_res)
         return dx, dgamma, dbeta, dres, None, None
 
 
 def batch_norm_fusable(features, bn):
     """True where batch_norm_act can take the place of ``bn`` (+ residual add + ReLU): a training-mode, affine nn.BatchNorm1d that
-    tracks running statistics with a fixed momentum, gradients enabled, fp32 device features [n >= 2, C] with a supported C."""
+    tracks running statistics with a fixed momentum, gradients enabled, fp32 or bf16 device features [n >= 2, C] with a supported C
+    (the parameters and buffers are fp32 either way)."""
     return (isinstance(bn, nn.BatchNorm1d) and bn.training and torch.is_grad_enabled() and bn.affine and bn.track_running_stats
-            and bn.momentum is not None and bn.running_mean is not None and features.is_cuda and features.dtype == torch.float32
+            and bn.momentum is not None and bn.running_mean is not None and features.is_cuda and features.dtype in (torch.float32, torch.bfloat16)
             and bn.weight.dtype == torch.float32 and bn.weight.device == features.device and features.dim() == 2
             and features.shape[0] >= 2 and hip_ops.sparse_bn_channels_ok(features.shape[1]))
 
@@ -217,10 +220,10 @@ def batch_norm_act(features, bn, residual=None, relu=True):
     buffers and state-dict keys unchanged).  Raises where batch_norm_fusable(features, bn) does not hold: there is no fallback here."""
     if not batch_norm_fusable(features, bn):
         raise hip_ops.FutureDetHipError("batch_norm_act: needs a training-mode affine BatchNorm1d with running statistics and a momentum, "
-                                        "gradients enabled and fp32 device features [n >= 2, C], C a multiple of 16 up to 128 (got %s %s)"
+                                        "gradients enabled and fp32 or bf16 device features [n >= 2, C], C a multiple of 16 up to 128 (got %s %s)"
                                         % (tuple(features.shape), features.dtype))
     if residual is not None:
-        residual = residual.float().contiguous()
+        residual = residual.to(features.dtype).contiguous()
     return _SparseBatchNormFunction.apply(features.contiguous(), bn.weight, bn.bias, residual, bn, bool(relu))
 
 

@@ -722,6 +722,10 @@ int fd_centerhead_loss_backward(const fd_loss_cfg *cfg, const fd_loss_task *task
  * Training: BatchNorm1d on batch statistics over the rows of a sparse feature matrix, fused with the ReLU and the residual add that
  * follow it in SpMiddleResNetFHD (fd_sparse_bn.hip).  Purely additive: fd_abi_version() stays 8.
  * fp32, row-major contiguous x [n, C]; C a multiple of 16 in [16, 128]; relu 0 or 1; residual [n, C] or NULL.
+ * The _bf16 entry points take bf16 rows (the bits, as uint16_t) for x, residual, y, dy, dx and d_residual; gamma, beta, saved, the
+ * running statistics, dgamma, dbeta and the workspace stay fp32 (one workspace size serves both).  A row is widened exactly on load
+ * and rounded to nearest even on store: the bf16 form computes what the fp32 form computes on the widened rows, rounded once.  The
+ * ReLU mask is y > 0 on the bf16 y; d_residual is the masked dy, copied.
  *   forward:  y = act(gamma (x - mean) invstd + beta [+ residual]);  mean and the biased variance over the valid rows,
  *             invstd = 1 / sqrt(var + eps);  saved = [mean[C], invstd[C]] fp32 for the backward;
  *             running_mean <- (1 - momentum) running_mean + momentum mean, running_var the same with the unbiased variance
@@ -748,6 +752,13 @@ int fd_sparse_bn_train_forward(const float *x, const float *residual, const floa
 int fd_sparse_bn_train_backward(const float *dy, const float *x, const float *y, const float *gamma, const float *saved, int64_t n,
                                 const int32_t *n_dev, int C, int relu, float *dx, float *d_residual, float *dgamma, float *dbeta,
                                 void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_sparse_bn_train_forward_bf16(const uint16_t *x, const uint16_t *residual, const float *gamma, const float *beta, int64_t n,
+                                    const int32_t *n_dev, int C, int relu, float eps, double momentum, uint16_t *y, float *saved,
+                                    float *running_mean, float *running_var, int64_t *num_batches_tracked, void *workspace,
+                                    size_t workspace_bytes, fd_stream_t stream);
+int fd_sparse_bn_train_backward_bf16(const uint16_t *dy, const uint16_t *x, const uint16_t *y, const float *gamma, const float *saved,
+                                     int64_t n, const int32_t *n_dev, int C, int relu, uint16_t *dx, uint16_t *d_residual, float *dgamma,
+                                     float *dbeta, void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
 #ifdef __cplusplus
 }
