@@ -57,6 +57,15 @@ def _reg_loss(output, mask, ind, target):
     return loss.transpose(2, 0).sum(dim=2).sum(dim=1)
 
 
+def _stack(modules, x, fused_bn):
+    """``modules(x)``; with CenterHead.fused_bn set, through dense_bn.run_stack (fusable BatchNorm2d + ReLU pairs on fd_dense_bn.hip)"""
+    if not fused_bn:
+        return modules(x)
+    from .dense_bn import run_stack
+
+    return run_stack(modules, x, True)
+
+
 class SepHead(nn.Module):
     def __init__(self, in_channels, heads, head_conv=64, final_kernel=1, bn=False, init_bias=-2.19, two_stage=False,
                  forecast_feature=False, wide_head=False, **kwargs):
@@ -90,17 +99,17 @@ class SepHead(nn.Module):
                         kaiming_init(m)
             self.__setattr__(head, fc)
 
-    def forward_modules(self, x):
+    def forward_modules(self, x, fused_bn=False):
         ret = {}
         if self.forecast_feature:
-            x = self.forecast_conv(x)
+            x = _stack(self.forecast_conv, x, fused_bn)
             ret["feats"] = x
         for head in self.heads:
-            ret[head] = self.__getattr__(head)(x)
+            ret[head] = _stack(self.__getattr__(head), x, fused_bn)
         return ret
 
-    def forward(self, x):
-        return self.forward_modules(x)
+    def forward(self, x, fused_bn=False):
+        return self.forward_modules(x, fused_bn)
 
 
 class DeformConv(nn.Module):
@@ -165,13 +174,13 @@ class DCNSepHead(nn.Module):
         self.cls_head[-1].bias.data.fill_(init_bias)
         self.task_head = SepHead(in_channels, heads, head_conv=head_conv, bn=bn, final_kernel=final_kernel)
 
-    def forward_modules(self, x):
+    def forward_modules(self, x, fused_bn=False):
         if self.training and x.is_cuda:
             a_cls, a_reg = self._adapt_pair_train(x)
         else:
             a_cls, a_reg = self.feature_adapt_cls(x), self.feature_adapt_reg(x)
-        ret = self.task_head(a_reg)
-        ret["hm"] = self.cls_head(a_cls)
+        ret = self.task_head(a_reg, fused_bn) if fused_bn else self.task_head(a_reg)
+        ret["hm"] = _stack(self.cls_head, a_cls, fused_bn)
         return ret
 
     def _adapt_pair_train(self, x):
@@ -186,8 +195,8 @@ class DCNSepHead(nn.Module):
         c = x.shape[1]
         return y[:, :c], y[:, c:]
 
-    def forward(self, x):
-        return self.forward_modules(x)
+    def forward(self, x, fused_bn=False):
+        return self.forward_modules(x, fused_bn)
 
 
 class _FusedLossFunction(torch.autograd.Function):
@@ -311,6 +320,7 @@ class CenterHead(nn.Module):
                                       forecast_feature=self.forecast_feature, wide_head=self.wide_head))
         self.compute_dtype = torch.float32
         self.fused_loss = False  # True: loss() of a standard / dense head runs on fd_loss.hip for fp32 maps on the device
+        self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the head runs on fd_dense_bn.hip (handed to the tasks)
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
         self.logger.info("Finish CenterHead Initialization")
@@ -327,14 +337,13 @@ class CenterHead(nn.Module):
         if self.dcn_head and self.training and x.is_cuda and self.compute_dtype != torch.float32:
             raise NotImplementedError("CenterHead(dcn_head=True): training runs in fp32 only; the %s head is inference-only (set "
                                       "compute_dtype = torch.float32 to train)" % self.compute_dtype)
-        x = self.shared_conv(x)
+        fused = bool(self.fused_bn)
+        x = _stack(self.shared_conv, x, fused)
         if self.bev_map:
-            x = x + self.bev_conv(bev_map)
+            x = x + _stack(self.bev_conv, bev_map, fused)
         for i, task in enumerate(self.tasks):
-            if i != 0 and self.forecast_feature:
-                ret_dicts.append(task(torch.cat([x, ret_dicts[i - 1]["feats"]], dim=1)))
-            else:
-                ret_dicts.append(task(x))
+            xin = torch.cat([x, ret_dicts[i - 1]["feats"]], dim=1) if i != 0 and self.forecast_feature else x
+            ret_dicts.append(task(xin, True) if fused else task(xin))
         return ret_dicts
 
     def forward(self, x, bev_map=None, *kwargs):

@@ -1432,3 +1432,59 @@ def sparse_bn_train_backward(dy, x, y, gamma, saved, relu=True, want_residual=Fa
     check(getattr(L, fn)(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), n, _p(n_dev), c, int(bool(relu)), _p(dx), _p(dres), _p(dgb[0]), _p(dgb[1]),
                          _p(ws), ws.numel(), _stream()), fn)
     return dx, dres, dgb[0], dgb[1]
+
+
+# ------------------------------------------------------------------------------------------------ dense BatchNorm (training)
+def dense_bn_chunk():
+    """Elements per chunk of the dense BatchNorm's sums (FD_DENSE_BN_CHUNK): part of the summation order."""
+    return int(_lib.load().fd_dense_bn_chunk())
+
+
+def _dense_bn_map(x, name):
+    """an fp32 NCHW-contiguous map on the device -> (tensor, B, C, P)"""
+    x = _dev(x, name, torch.float32)
+    if x.dim() != 4:
+        raise FutureDetHipError("%s must be [B, C, H, W], got %s" % (name, tuple(x.shape)))
+    return x, x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
+
+
+def _dense_bn_ws(L, b, c, p, device):
+    return workspace.get("dense_bn", L.fd_dense_bn_workspace_bytes(int(b), int(c), int(p)), device)
+
+
+def dense_bn_train_forward(x, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, relu=True):
+    """fd_dense_bn_train_forward: y = act(gamma (x - mean) invstd + beta) on batch statistics over x [B, C, H, W], fp32 NCHW contiguous;
+    updates running_mean / running_var / num_batches_tracked in place on the device (their ``_version`` is NOT bumped: the caller
+    does that).  Returns (y, saved [2, C] = mean, invstd).  Two launches, nothing is synchronised."""
+    L = _lib.load()
+    x, b, c, p = _dense_bn_map(x, "x")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if _dev(t, name, torch.float32).numel() != c:
+            raise FutureDetHipError("%s must hold %d channels, got %d" % (name, c, t.numel()))
+    _dev(num_batches_tracked, "num_batches_tracked", torch.int64)
+    out = torch.empty_like(x)
+    saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws = _dense_bn_ws(L, b, c, p, x.device)
+    check(L.fd_dense_bn_train_forward(_p(x), _p(gamma), _p(beta), b, c, p, int(bool(relu)), float(eps), float(momentum), _p(out), _p(saved),
+                                      _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel(), _stream()),
+          "fd_dense_bn_train_forward")
+    return out, saved
+
+
+def dense_bn_train_backward(dy, x, y, gamma, saved, relu=True):
+    """fd_dense_bn_train_backward: -> (dx, dgamma, dbeta).  ``y`` is the forward's output (the ReLU mask; may be None with relu=False),
+    ``saved`` what the forward returned."""
+    L = _lib.load()
+    x, b, c, p = _dense_bn_map(x, "x")
+    dy = _dev(dy, "dy", torch.float32)
+    if dy.shape != x.shape or (y is not None and _dev(y, "y", torch.float32).shape != x.shape):
+        raise FutureDetHipError("dy and y must be %s" % (tuple(x.shape),))
+    if _dev(saved, "saved", torch.float32).numel() != 2 * c or _dev(gamma, "gamma", torch.float32).numel() != c:
+        raise FutureDetHipError("gamma / saved do not hold %d channels" % c)
+    dx = torch.empty_like(x)
+    # two tensors, not two rows of one: autograd keeps a gradient that owns its storage and would copy a view
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+    ws = _dense_bn_ws(L, b, c, p, x.device)
+    check(L.fd_dense_bn_train_backward(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), b, c, p, int(bool(relu)), _p(dx), _p(dgamma), _p(dbeta),
+                                       _p(ws), ws.numel(), _stream()), "fd_dense_bn_train_backward")
+    return dx, dgamma, dbeta

@@ -187,6 +187,12 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fd_sparse_bn_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_int,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_dense_bn_chunk": (c_int, []),
+    "fd_dense_bn_workspace_bytes": (c_size_t, [c_i64, c_int, c_i64]),
+    "fd_dense_bn_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_float, ctypes.c_double,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_dense_bn_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 for _name in ("fd_sparse_bn_train_forward", "fd_sparse_bn_train_backward"):  # bf16 rows: the same argument lists
     SIGNATURES[_name + "_bf16"] = SIGNATURES[_name]

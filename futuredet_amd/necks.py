@@ -55,6 +55,7 @@ class RPN(nn.Module):
         self.blocks = nn.ModuleList(blocks)
         self.deblocks = nn.ModuleList(deblocks)
         self.compute_dtype = torch.float32
+        self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the blocks and deblocks runs on fd_dense_bn.hip
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
         (logger or logging.getLogger("RPN")).info("Finish RPN Initialization")
@@ -80,12 +81,19 @@ class RPN(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.xavier_uniform_(m.weight)
 
+    def _stack(self, modules, x):
+        if not self.fused_bn:
+            return modules(x)
+        from .dense_bn import run_stack
+
+        return run_stack(modules, x, True)
+
     def forward_modules(self, x):
         ups = []
         for i in range(len(self.blocks)):
-            x = self.blocks[i](x)
+            x = self._stack(self.blocks[i], x)
             if i >= self.first_up:
-                ups.append(self.deblocks[i - self.first_up](x))
+                ups.append(self._stack(self.deblocks[i - self.first_up], x))
         if len(ups) > 0:
             x = torch.cat(ups, dim=1)
         return x

@@ -760,6 +760,37 @@ int fd_sparse_bn_train_backward_bf16(const uint16_t *dy, const uint16_t *x, cons
                                      int64_t n, const int32_t *n_dev, int C, int relu, uint16_t *dx, uint16_t *d_residual, float *dgamma,
                                      float *dbeta, void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Training: BatchNorm2d on batch statistics over the maps of the dense half (RPN, CenterHead), fused with the ReLU that follows it
+ * (fd_dense_bn.hip).  Purely additive: fd_abi_version() stays 8.
+ * fp32, NCHW contiguous x [B, C, H, W], passed as (B, C, P = H W); N = B P values per channel.  C in [1, 4096] (no multiple-of-16
+ * rule: the channel is not the vectorised axis), B in [1, 2^16], P in [1, 2^30], B C <= 2^24, B ceil(P / chunk) <= 2^29, N >= 2;
+ * relu 0 or 1.  Element offsets are 64-bit.  No residual input, no bf16 form.
+ *   forward:  y = act(gamma[c] (x - mean[c]) invstd[c] + beta[c]);  saved [2, C] = (mean, invstd) for the backward;
+ *             running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the unbiased variance
+ *             var N / (N - 1), num_batches_tracked (int64) += 1 -- all on the device.
+ *   backward: g = dy where y > 0 (relu = 1; y is the forward's output) or dy;  dbeta = sum g;  dgamma = sum g x^,
+ *             x^ = (x - mean) invstd;  dx = gamma invstd (g - dbeta / N - x^ dgamma / N).
+ * Sums: every plane (b, c) is cut into chunks of fd_dense_bn_chunk() (= FD_DENSE_BN_CHUNK) elements; a channel's chunks, ordered by
+ * (b, piece), form groups of consecutive chunks; a chunk's partial is centred at the chunk's own mean; partials are combined in double,
+ * in a fixed order, with Chan's rule.  No atomics, and every boundary follows from (B, C, P): the same bits on every run.
+ * P % 4 == 0: all traffic is 16-byte loads and stores; any other P runs element by element (plane starts are then unaligned).
+ * Two launches per call; no allocation, no synchronisation.  workspace >= fd_dense_bn_workspace_bytes(B, C, P) (0 = unsupported
+ * sizes), 16-byte aligned; the backward does not need the forward's contents.
+ * Both entry points validate on the host before any device work; FD_EINVAL for: a null pointer (other than y when relu = 0), C, B or P
+ * out of range, B P < 2, relu not 0 or 1, eps <= 0, momentum outside [0, 1], a workspace that is null, too small or misaligned,
+ * x, y, dy or dx not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_DENSE_BN_CHUNK 2048
+int fd_dense_bn_chunk(void);
+size_t fd_dense_bn_workspace_bytes(int64_t B, int C, int64_t P);
+int fd_dense_bn_train_forward(const float *x, const float *gamma, const float *beta, int64_t B, int C, int64_t P, int relu, float eps,
+                              double momentum, float *y, float *saved, float *running_mean, float *running_var,
+                              int64_t *num_batches_tracked, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_dense_bn_train_backward(const float *dy, const float *x, const float *y, const float *gamma, const float *saved, int64_t B, int C,
+                               int64_t P, int relu, float *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                               fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
