@@ -7,6 +7,10 @@
 // One wave per pillar.  Layer 1: lane = (point group g, unit u), its weight row in registers, the decorated point
 // broadcast from LDS.  Layer 2 (64 units): lane = unit; the half of the input that is the repeated per-pillar max
 // (pillar_encoder.py:52-54) contributes one per-pillar constant, so only U1 products per point remain.
+//
+// num_points == 0 (the voxelizer never emits such a pillar): the mean divides by zero, but the padding mask is a select,
+// not the reference's multiplication by 0, so every row is masked to 0 and the pillar comes out finite -- relu(shift) of
+// layer 1 fed through the rest -- where the reference yields NaN.  tests/test_gpu_pillars_eval.py pins this.
 #include "fd_common.h"
 
 namespace {
