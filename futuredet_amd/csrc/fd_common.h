@@ -33,11 +33,9 @@ struct SpconvCall {
     hipStream_t stream;
 };
 
-// The buffer fd_spconv_pack_weight / fd_spconv_pack_weight_device write and the kernels read, as byte sections (bytes 0 = absent):
-//   base  [K][cin / 16 (bf16, cin >= 32: cin / 32)][cout / 16][64 lanes] fragments of the 16x16 MFMAs: every shape
-//   c32   fp32 32 -> 32: the 32x32x2 fragment order of fd_spconv_c32.hip
-//   pair  bf16 with 16 input channels: two taps stacked along K = 32 (fd_spconv_bf16.hip), ceil(K / 2) tap pairs
-//   win   bf16 64 -> 64 and 128 -> 128: the 32x32x16 fragment order of the LDS-window kernel (fd_spconv_bf16win.hip)
+constexpr int kSpconvMaxTaps = 27;  // 3 x 3 x 3: the largest kernel of every sparse-convolution entry point
+
+// The byte sections of the packed-weight buffer (bytes 0 = absent); what they hold and in which order: fd_spconv_pack.h
 struct WeightSection {
     size_t offset, bytes;
 };
@@ -69,13 +67,6 @@ int spconv_f32_c32_dispatch(const SpconvCall &c);      // fd_spconv_c32.hip: fp3
 int spconv_f32_compact_dispatch(const SpconvCall &c);  // fd_spconv_v2.hip: fp32, pair compaction
 int spconv_bf16_win_dispatch(const SpconvCall &c);     // fd_spconv_bf16win.hip: 64 -> 64, 128 -> 128 with an LDS window of input rows and 32-row MFMA tiles
 int spconv_bf16_ws_dispatch(const SpconvCall &c);      // fd_spconv_bf16.hip: RESIDENT / RING kernels
-// fd_spconv_bf16win.hip: writes the win section
-void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*tobf)(float), uint16_t *dst);
-// Output rows per workgroup and per partial of the weight gradients (fd_spconv_grad.hip, fd_spconv_grad_bf16.hip): part of the summation
-// order, not a tuning knob; the shared second kernel derives the number of used chunks from it
-constexpr int kSpconvWgradChunk = 512;
-// fd_spconv_grad.hip: the second kernel of the weight gradients -- dw[k][e] = the tap's per-chunk partials [K][n_chunks][cc], summed in chunk order
-void spconv_wgrad_reduce(const float *partial, int K, int cc, int n_out, const int *n_out_dev, int n_chunks, float *dw, hipStream_t stream);
 
 // fd_conv2d_wino_pc.hip: 0 = launched, 1 = shape not supported by the variant, -1 = dynamic LDS refused; wide_items: work items of 128
 // output channels (tile 8) instead of 64 (tile 7)

@@ -55,7 +55,8 @@ __device__ __forceinline__ float4 ld4(const bf16_t *p) {
                        __uint_as_float(u.y & 0xffff0000u));
 }
 __device__ __forceinline__ float ld1(const bf16_t *p) { return __uint_as_float((unsigned)*p << 16); }
-// round to nearest even (fd_spconv_grad_bf16.hip's to_bf16_rne); a NaN stays a NaN instead of carrying into the sign
+// round to nearest even as fd::bf16_rne (fd_spconv_pack.h) does, and a copy of its own because here a NaN stays a NaN instead of
+// carrying into the sign
 __device__ __forceinline__ unsigned to_bf16_rne(float v) {
     const unsigned u = __float_as_uint(v);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;

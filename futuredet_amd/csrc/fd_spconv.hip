@@ -14,7 +14,7 @@
 // lane>>4); B operands come from weights pre-packed in fragment order, one coalesced 1 KiB load per wave
 // instruction (L2-resident: at most 1.8 MB per layer).  fp32 uses v_mfma_f32_16x16x4_f32 (exact fp32 fma
 // chain), bf16 uses v_mfma_f32_16x16x32_bf16 / 16x16x16 with fp32 accumulation.
-#include "fd_common.h"
+#include "fd_spconv_pack.h"
 
 namespace {
 
@@ -29,7 +29,6 @@ __device__ inline unsigned short f2bf(float v) {
 }
 __device__ inline float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
 
-constexpr int kMaxTaps = 27;
 
 // ------------------------------------------------------------------------------------------------- fp32
 template <int CIN, int COUT, int RG>
@@ -39,7 +38,7 @@ __global__ void __launch_bounds__(256) spconv_f32(const float *__restrict__ in, 
                                                   const int *__restrict__ n_out_dev, float *__restrict__ out) {
     constexpr int ROWS_B = 64 * RG;  // rows per workgroup
     constexpr int NB = COUT / 16, NC = CIN / 16;
-    __shared__ int s_nbr[kMaxTaps * ROWS_B];
+    __shared__ int s_nbr[fd::kSpconvMaxTaps * ROWS_B];
     const int tile = blockIdx.x;  // index order: contiguous XCD chunks concentrate the dense regions on a few XCDs (measured -10%)
     const int row0 = tile * ROWS_B;
     n_out = fd::device_count(n_out, n_out_dev);  // capacity launch (fd_common.h): workgroups past the device's count leave
@@ -129,7 +128,7 @@ __global__ void __launch_bounds__(256) spconv_bf16(const unsigned short *__restr
     constexpr int NB = COUT / 16;
     constexpr bool WIDE = CIN >= 32;
     constexpr int NC = WIDE ? CIN / 32 : 1;
-    __shared__ int s_nbr[kMaxTaps * ROWS_B];
+    __shared__ int s_nbr[fd::kSpconvMaxTaps * ROWS_B];
     const int tile = blockIdx.x;  // index order: contiguous XCD chunks concentrate the dense regions on a few XCDs (measured -10%)
     const int row0 = tile * ROWS_B;
     n_out = fd::device_count(n_out, n_out_dev);  // capacity launch (fd_common.h): workgroups past the device's count leave
@@ -258,77 +257,17 @@ extern "C" size_t fd_spconv_packed_weight_bytes(int K, int cin, int cout, int dt
     return fd::spconv_weight_layout(K, cin, cout, dtype).total;
 }
 
+// the element order: fd_spconv_pack.h
 extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, int dtype, void *dst) {
-    FD_REQUIRE(w && dst, "fd_spconv_pack_weight: null argument");
-    FD_REQUIRE(K >= 1 && K <= kMaxTaps, "fd_spconv_pack_weight: K must be in [1,27]");
-    FD_REQUIRE(cin % 16 == 0 && cout % 16 == 0 && cin >= 16 && cin <= 128 && cout >= 16 && cout <= 128,
-               "fd_spconv_pack_weight: channels must be multiples of 16 in [16,128] (got %d -> %d)", cin, cout);
-    FD_REQUIRE(dtype == 0 || dtype == 1, "fd_spconv_pack_weight: dtype must be 0 (f32) or 1 (bf16)");
-    const int NB = cout / 16;
-    const fd::SpconvWeightLayout lay = fd::spconv_weight_layout(K, cin, cout, dtype);
-    auto W = [&](int k, int ci, int co) { return w[((int64_t)k * cin + ci) * cout + co]; };
-    auto tobf = [](float v) -> uint16_t {
-        union { float f; uint32_t u; } cvt;
-        cvt.f = v;
-        uint32_t u = cvt.u;
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    };
-    if (dtype == 0) {
-        const int NC = cin / 16;
-        float *d = (float *)dst;
-        for (int k = 0; k < K; ++k)
-            for (int c = 0; c < NC; ++c)
-                for (int nb = 0; nb < NB; ++nb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            d[((((int64_t)k * NC + c) * NB + nb) * 64 + lane) * 4 + j] =
-                                W(k, 16 * c + 4 * (lane >> 4) + j, 16 * nb + (lane & 15));
-        if (lay.c32.bytes) {  // [K][cin / 8][lane][4]: channel 8 c + 4 (lane / 32) + j, output channel lane % 32
-            float *e = (float *)((char *)dst + lay.c32.offset);
-            for (int k = 0; k < K; ++k)
-                for (int c = 0; c < cin / 8; ++c)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            e[(((int64_t)k * (cin / 8) + c) * 64 + lane) * 4 + j] = W(k, 8 * c + 4 * (lane >> 5) + j, lane & 31);
-        }
-    } else if (cin >= 32) {
-        FD_REQUIRE(cin % 32 == 0, "fd_spconv_pack_weight: bf16 needs cin 16 or a multiple of 32");
-        const int NC = cin / 32;
-        uint16_t *d = (uint16_t *)dst;
-        for (int k = 0; k < K; ++k)
-            for (int c = 0; c < NC; ++c)
-                for (int nb = 0; nb < NB; ++nb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j)
-                            d[((((int64_t)k * NC + c) * NB + nb) * 64 + lane) * 8 + j] =
-                                tobf(W(k, 32 * c + 8 * (lane >> 4) + j, 16 * nb + (lane & 15)));
-        // the LDS-window kernel's 32x32x16 fragment order follows (fd_spconv_bf16win.hip)
-        if (lay.win.bytes) fd::spconv_bf16_win_pack(w, K, cin, cout, +tobf, (uint16_t *)((char *)dst + lay.win.offset));
-    } else {
-        uint16_t *d = (uint16_t *)dst;
-        for (int k = 0; k < K; ++k)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j)
-                        d[(((int64_t)k * NB + nb) * 64 + lane) * 4 + j] = tobf(W(k, 4 * (lane >> 4) + j, 16 * nb + (lane & 15)));
-        // tap pairs [ceil(K/2)][NB][lane][8]: quads 0,1 = channels 0..7 / 8..15 of tap 2u, quads 2,3 = those of tap 2u + 1 (zeros past K)
-        uint16_t *e = (uint16_t *)((char *)dst + lay.pair.offset);
-        for (int u = 0; u < (K + 1) / 2; ++u)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int q = lane >> 4, k = 2 * u + (q >> 1);
-                        e[(((int64_t)u * NB + nb) * 64 + lane) * 8 + j] = k < K ? tobf(W(k, 8 * (q & 1) + j, 16 * nb + (lane & 15))) : (uint16_t)0;
-                    }
-    }
+    if (const int rc = fd::spconv_pack_check("fd_spconv_pack_weight", w, dst, K, cin, cout, dtype, 0)) return rc;
+    fd::spconv_pack_weight_host(w, K, cin, cout, dtype, dst);
     return FD_OK;
 }
 
 extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
                                const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
                                const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats, fd_stream_t stream) {
-    FD_REQUIRE(K >= 1 && K <= kMaxTaps, "fd_spconv_apply: K must be in [1,27]");
+    FD_REQUIRE(K >= 1 && K <= fd::kSpconvMaxTaps, "fd_spconv_apply: K must be in [1,27]");
     FD_REQUIRE(dtype == 0 || dtype == 1, "fd_spconv_apply: dtype must be 0 (f32) or 1 (bf16)");
     FD_REQUIRE(n_out >= 0 && n_out <= nbr_stride && n_out < (1ll << 31), "fd_spconv_apply: n_out out of range");
     FD_REQUIRE(n_ranges >= 0 && (ranges == nullptr || n_ranges >= 1), "fd_spconv_apply: ranges needs n_ranges >= 1");

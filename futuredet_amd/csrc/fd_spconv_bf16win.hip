@@ -490,21 +490,7 @@ extern "C" int fd_debug_set_wintrace(void *p) { return hipMemcpyToSymbol(HIP_SYM
 #endif
 
 namespace fd {
-// [K][H halves][KS k-steps][CB column blocks][lane][8] bf16: lane (m = lane % 32, kg = lane / 32) element j of fragment
-// (tap, h, s, cb) = W[tap][input channel SC h + 16 s + 8 kg + j][output channel 32 cb + m] -- the A operand of v_mfma_f32_32x32x16_bf16
-void spconv_bf16_win_pack(const float *w, int K, int cin, int cout, uint16_t (*tobf)(float), uint16_t *dst) {
-    const int SC = cin < 64 ? cin : 64, H = cin / SC, KS = SC / 16, CB = cout / 32;
-    for (int k = 0; k < K; ++k)
-        for (int h = 0; h < H; ++h)
-            for (int s = 0; s < KS; ++s)
-                for (int cb = 0; cb < CB; ++cb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int ci = SC * h + 16 * s + 8 * (lane >> 5) + j, co = 32 * cb + (lane & 31);
-                            dst[((((((int64_t)k * H + h) * KS + s) * CB + cb) * 64) + lane) * 8 + j] = tobf(w[((int64_t)k * cin + ci) * cout + co]);
-                        }
-}
-
+// the win section's fragment order [K][H halves][KS k-steps][CB column blocks][lane][8]: fd_spconv_pack.h
 // returns 1 when launched, 0 when the shape is not covered (the caller takes the RING / RESIDENT kernels)
 int spconv_bf16_win_dispatch(const SpconvCall &a) {
     if (!spconv_weight_layout(a).win.bytes) return 0;

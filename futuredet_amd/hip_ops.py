@@ -369,6 +369,10 @@ def pack_spconv_weight(w_kio, dtype=torch.float32):
 
 
 PACK_PLAIN, PACK_TRANSPOSED, PACK_FLIPPED_TRANSPOSED = 0, 1, 2  # fd_spconv_pack_weight_device modes: W[k], W[k]^T, W[K-1-k]^T
+# per row dtype: the device packer, and (entry point, workspace function, workspace tag) of the weight gradient
+_PACK_DEVICE = {torch.float32: "fd_spconv_pack_weight_device", torch.bfloat16: "fd_spconv_pack_weight_device_bf16"}
+_WGRAD = {torch.float32: ("fd_spconv_wgrad", "fd_spconv_wgrad_workspace_bytes", "spconv_wgrad"),
+          torch.bfloat16: ("fd_spconv_wgrad_bf16", "fd_spconv_wgrad_bf16_workspace_bytes", "spconv_wgrad_bf16")}
 
 
 def pack_spconv_weight_device(w_kio, mode=PACK_PLAIN, dtype=torch.float32):
@@ -381,10 +385,8 @@ def pack_spconv_weight_device(w_kio, mode=PACK_PLAIN, dtype=torch.float32):
     K, cin, cout = w.shape
     ci, co = (cout, cin) if mode else (cin, cout)
     out = torch.empty((L.fd_spconv_packed_weight_bytes(K, ci, co, _DT[dtype]),), dtype=torch.uint8, device=w.device)
-    if dtype == torch.float32:
-        check(L.fd_spconv_pack_weight_device(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device")
-    else:
-        check(L.fd_spconv_pack_weight_device_bf16(_p(w), K, cin, cout, int(mode), _p(out), _stream()), "fd_spconv_pack_weight_device_bf16")
+    name = _PACK_DEVICE[dtype]
+    check(getattr(L, name)(_p(w), K, cin, cout, int(mode), _p(out), _stream()), name)
     return out
 
 
@@ -400,14 +402,10 @@ def spconv_wgrad(feats, dy, nbr, n_out):
     cin, cout = feats.shape[1], dy.shape[1]
     assert dy.shape[0] >= n_out
     dw = torch.empty((K, cin, cout), dtype=torch.float32, device=feats.device)
-    if feats.dtype == torch.float32:
-        ws = workspace.get("spconv_wgrad", L.fd_spconv_wgrad_workspace_bytes(K, n_out, cin, cout), feats.device)
-        check(L.fd_spconv_wgrad(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
-                                _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad")
-    else:
-        ws = workspace.get("spconv_wgrad_bf16", L.fd_spconv_wgrad_bf16_workspace_bytes(K, n_out, cin, cout), feats.device)
-        check(L.fd_spconv_wgrad_bf16(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
-                                     _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), "fd_spconv_wgrad_bf16")
+    name, ws_bytes, tag = _WGRAD[feats.dtype]
+    ws = workspace.get(tag, getattr(L, ws_bytes)(K, n_out, cin, cout), feats.device)
+    check(getattr(L, name)(_p(feats), feats.shape[0], _p(dy), _p(_dev(nbr, "nbr", torch.int32)), nstride, K, n_out,
+                           _p(getattr(nbr, "n_dev", None)), cin, cout, _p(dw), _p(ws), ws.numel(), _stream()), name)
     return dw
 
 

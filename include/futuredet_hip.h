@@ -481,7 +481,8 @@ int fd_deform_adapt_pack_weight_device(const float *w_cls_oihw, const float *w_r
 /* ---------------------------------------------------------------------------------------------------
  * Training: the backward pass of the fp32 sparse convolution (fd_spconv_grad.hip) -- spconv 1.0's indice_conv_backward /
  * indice_subm_conv_backward (gradients of scn.py:99-141 under loss.backward()).  Purely additive: fd_abi_version() stays 8.
- * fp32 only; cin, cout in {16, 32, 64, 128}.
+ * fp32 only; cin, cout in {16, 32, 64, 128}.  The weight gradient's kernel and entry-point body are shared with the bf16 rows below
+ * (fd_spconv_wgrad.h); the element order of the packed weights, for the host packer and both device packers: fd_spconv_pack.h.
  *   fd_spconv_wgrad:  dw[k] = sum_o in[nbr[k][o]]^T . dy[o]  ([K, cin, cout] fp32, overwritten) for the output-stationary table of
  *                     fd_rulebook; dy [n_out, cout].  Deterministic: per-(512-row chunk, tap) partials in `workspace`
  *                     (fd_spconv_wgrad_workspace_bytes), summed in chunk order -- bit-identical whatever the launch.  n_out_dev as in
@@ -508,7 +509,8 @@ int fd_dense_gather(const float *dense, int64_t stride_b, int64_t stride_c, int6
  * Mixed-precision training of the sparse convolution (fd_spconv_grad_bf16.hip): bf16 rows, fp32 master weights and gradients.
  * Purely additive: fd_abi_version() stays 8.  The forward is fd_spconv_apply(dtype 1); the input gradient is fd_spconv_apply(dtype 1)
  * on the transposed problem exactly as above, for which the bf16 kernels also take 32 -> 16, 64 -> 32 and 128 -> 64.
- *   fd_spconv_wgrad_bf16:  fd_spconv_wgrad with bf16 in_feats [n_in, cin] and dy [n_out, cout]; dw [K, cin, cout] stays FP32 (overwritten).
+ *   fd_spconv_wgrad_bf16:  fd_spconv_wgrad (the same kernel skeleton and summation order, fd_spconv_wgrad.h) with bf16 in_feats [n_in, cin]
+ *                     and dy [n_out, cout]; dw [K, cin, cout] stays FP32 (overwritten).
  *                     bf16 x bf16 products accumulated in fp32 on the matrix core.  (cin, cout) in {16->16, 16->32, 32->32, 32->64, 64->64,
  *                     64->128, 128->128}.  The same per-(512-row chunk, tap) partials in `workspace`
  *                     (fd_spconv_wgrad_bf16_workspace_bytes; 0 = bad sizes), summed in chunk order: bit-identical whatever the launch, no

@@ -146,7 +146,7 @@ def test_device_pack_is_byte_identical_to_the_host_pack(cin, cout):
     from futuredet_amd import hip_ops
 
     g = torch.Generator().manual_seed(cin * 7 + cout)
-    for K in (27, 3):
+    for K in (27, 3, 1, 2):
         w = torch.randn((K, cin, cout), generator=g)
         wd = w.to(DEV)
         cases = ((hip_ops.PACK_PLAIN, w), (hip_ops.PACK_TRANSPOSED, w.transpose(1, 2)), (hip_ops.PACK_FLIPPED_TRANSPOSED, w.flip(0).transpose(1, 2)))
@@ -156,12 +156,18 @@ def test_device_pack_is_byte_identical_to_the_host_pack(cin, cout):
             assert got.shape == want.shape and torch.equal(got, want), (K, cin, cout, mode)
 
 
-@pytest.mark.parametrize("cin,cout", [(16, 16), (16, 32), (64, 128), (128, 128)])
+# every instantiation has its own tile split: four on a 10000-row table, the rest on a small one -- about 1300 rows, i.e. three 512-row
+# chunks with a partial last one, last batches with a zero-padded tail, and (below) a device count that ends inside the second chunk
+WGRAD_TABLES = {True: ((21, 48, 48), 5000), False: ((9, 24, 24), 650)}  # grid, voxels per sample
+
+
+@pytest.mark.parametrize("cin,cout", [(a, b) for a in (16, 32, 64, 128) for b in (16, 32, 64, 128)])
 def test_wgrad_is_deterministic_and_takes_a_device_count(cin, cout):
     from futuredet_amd import hip_ops
 
     rng = np.random.default_rng(cin + cout)
-    src, dst, nbr = _rulebook(rng, 2, (21, 48, 48), 5000, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
+    grid, nvox = WGRAD_TABLES[(cin, cout) in ((16, 16), (16, 32), (64, 128), (128, 128))]
+    src, dst, nbr = _rulebook(rng, 2, grid, nvox, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
     feats = torch.from_numpy(rng.uniform(-1, 1, (src.n, cin)).astype(np.float32)).to(DEV)
     dy = torch.from_numpy(rng.uniform(-1, 1, (dst.n, cout)).astype(np.float32)).to(DEV)
     a = hip_ops.spconv_wgrad(feats, dy, nbr, dst.n)

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from parity_util import assert_close, report
-from test_gpu_spconv_grad import LAYERS
+from test_gpu_spconv_grad import LAYERS, WGRAD_TABLES
 
 pytestmark = pytest.mark.gpu
 
@@ -158,7 +158,7 @@ def test_device_bf16_pack_is_byte_identical_to_the_host_pack(cin, cout):
     from futuredet_amd import hip_ops
 
     g = torch.Generator().manual_seed(cin * 7 + cout)
-    for K in (27, 3):
+    for K in (27, 3, 1, 2):
         w = torch.randn((K, cin, cout), generator=g)
         # every third value exactly half way between two bf16 neighbours (ties to even, both parities), every seventh one ulp off a tie
         bits = w.view(torch.int32).clone()
@@ -200,12 +200,13 @@ def test_transposed_shapes_on_a_transposed_table(cbig, csmall, geom):
 
 
 # ------------------------------------------------------------------------------------------------ 4. determinism, launch independence
-@pytest.mark.parametrize("cin,cout", [(16, 16), (16, 32), (32, 64), (128, 128)])
+@pytest.mark.parametrize("cin,cout", FORWARD_SHAPES)
 def test_wgrad_bf16_is_deterministic_and_independent_of_the_launch(cin, cout):
     from futuredet_amd import hip_ops
 
     rng = np.random.default_rng(cin + cout)
-    src, dst, nbr = _rulebook(rng, 2, (21, 48, 48), 5000, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
+    grid, nvox = WGRAD_TABLES[(cin, cout) in ((16, 16), (16, 32), (32, 64), (128, 128))]  # the small table: see test_gpu_spconv_grad.py
+    src, dst, nbr = _rulebook(rng, 2, grid, nvox, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
     feats = _bf16_values(rng, (src.n, cin)).to(DEV).to(BF)
     dy = _bf16_values(rng, (dst.n, cout)).to(DEV).to(BF)
     a = hip_ops.spconv_wgrad(feats, dy, nbr, dst.n)

@@ -317,7 +317,8 @@ def test_product_path_fails_loudly_without_gpu_tensors():
 
 
 def test_weight_packing_layout():
-    """fd_spconv_pack_weight is host code: check the fragment order documented in fd_spconv.hip."""
+    """fd_spconv_pack_weight is host code: check the fragment order documented in fd_spconv_pack.h (every section and shape:
+    test_spconv_pack_host.py)."""
     import ctypes
 
     L = lib.load()
