@@ -259,6 +259,53 @@ class SpMiddleResNetFHD(nn.Module):
         bev = hip_ops.densify(x, idx[4], out_dtype=self.dense_dtype or dt, channels_last=self.dense_channels_last, out=dense_out)
         return bev, levels
 
+    def forward_static_train(self, feats0, idx):
+        """The train-mode walk of _stages() over a finished index pyramid (hip_ops.build_pyramid): what forward_generic computes, with
+        no host read.  ``feats0`` [idx[0].n, 16]: the level-0 rows in index order, channel padded (fp32, or already ``train_dtype``);
+        ``idx``: the five indexes.  With static indexes (``static=True, row_caps=...``) every ``idx[l].n`` is a row CAPACITY and every
+        kernel -- convolutions, weight and bias gradients, BatchNorm in both directions, densify's backward -- takes the level's count
+        from the device; with host-sized indexes the calls are forward_generic's own.  The same autograd functions either way, so
+        the BEV map, the running statistics and the gradients carry the same bits (bias gradients: fd_rows_colsum's summation
+        order instead of torch's).  Single stream; the rulebooks are built where they are first used.
+        Needs ``fused_bn = True``: the torch BatchNorm chain cannot honour a device count.  Returns the BEV map [B, 128 * D, H, W]."""
+        if not self.fused_bn:
+            raise ValueError("SpMiddleResNetFHD.forward_static_train needs fused_bn = True: torch's BatchNorm1d cannot take its row count "
+                             "from the device (set backbone.fused_bn = True)")
+        if not (self.training and torch.is_grad_enabled()):
+            raise RuntimeError("SpMiddleResNetFHD.forward_static_train is the training path: call .train() and enable gradients")
+        if self.train_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("SpMiddleResNetFHD: train_dtype must be torch.float32 or torch.bfloat16 (got %s)" % (self.train_dtype,))
+        B = idx[0].B
+        feats = feats0.to(self.train_dtype)
+        rulebooks = {}
+
+        def conv(m, x, src, dst):
+            ks, st, pd = m.geometry()
+            key = (id(src), id(dst), tuple(ks), tuple(st), tuple(pd))  # a level's SubM convolutions share one table, as under an indice_key
+            if key not in rulebooks:
+                rulebooks[key] = src.rulebook(dst, ks, st, pd)
+            return m._forward_autograd(x, dst, rulebooks[key])
+
+        def bn_act(x, bn, dst, residual=None):
+            if dst.n < 2 or not spconv.batch_norm_fusable(x.features, bn):
+                raise hip_ops.FutureDetHipError("forward_static_train: BatchNorm over %s %s rows cannot run on the fused kernels"
+                                                % (tuple(x.features.shape), x.features.dtype))
+            x.features = spconv.batch_norm_act(x.features, bn, residual=residual, relu=True, n_dev=dst.n_dev if dst.static else None)
+            return x
+
+        x = spconv.SparseConvTensor(feats, None, idx[0].spatial_shape, B, _index=idx[0])
+        for lvl, (head, bn, blocks, is_subm_in) in enumerate(self._stages()):
+            src, dst = (idx[lvl] if is_subm_in else idx[lvl - 1]), idx[lvl]
+            x = bn_act(conv(head, x, src, dst), bn, dst)
+            for blk in blocks:
+                y = bn_act(conv(blk.conv1, x, dst, dst), blk.bn1, dst)
+                x = bn_act(conv(blk.conv2, y, dst, dst), blk.bn2, dst, residual=x.features)
+        ret = x.dense()
+        if ret.dtype != torch.float32:
+            ret = ret.float()  # the neck trains in fp32
+        N, C, D, H, W = ret.shape
+        return ret.view(N, C * D, H, W)
+
     def forward(self, voxel_features, coors, batch_size, input_shape):
         if self.training:
             if self.train_dtype not in (torch.float32, torch.bfloat16):

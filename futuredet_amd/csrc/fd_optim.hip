@@ -17,6 +17,8 @@
 //                  floats it hands to addcdiv_ / div.
 //   optim_step     chunk c: decay, moments, update.
 // Every sum has one fixed order that depends on the table alone: no atomics, the same bits on every run.
+// fd_optim_adam_step_dev launches the same three kernels with the scalars behind a device pointer and an optional device skip flag
+// (a step captured into a graph: the schedule changes lr and beta1 at every replay, and an overflowed replay must not train).
 //
 // Built with -ffp-contract=off: the fp32 expression of the header is what runs (torch's kernels do not contract either).
 #include <math.h>
@@ -35,6 +37,22 @@ static_assert(kChunk % (kThreads * 4) == 0, "a chunk is a whole number of 16-byt
 struct Hyper {  // launch argument: lr and beta1 change at every iteration
     double lr, beta1, beta2, eps, wd, max_norm;
 };
+
+// Where a launch finds its scalars: in its arguments (fd_optim_adam_step), or in a device record of six doubles in Hyper's order
+// (fd_optim_adam_step_dev: a captured launch bakes its arguments in, the record is read at every replay).  Both ways hand the kernels the
+// same doubles, so both round them alike.  `skip` (device, may be null): non-zero = the call leaves everything but norm as it is.
+struct HyperSource {
+    Hyper h;
+    const double *dev;
+    const int32_t *skip;
+};
+__device__ __forceinline__ Hyper load_hyper(const HyperSource &s) {
+    if (!s.dev) return s.h;
+    Hyper h;
+    h.lr = s.dev[0]; h.beta1 = s.dev[1]; h.beta2 = s.dev[2]; h.eps = s.dev[3]; h.wd = s.dev[4]; h.max_norm = s.dev[5];
+    return h;
+}
+__device__ __forceinline__ bool skipped(const HyperSource &s) { return s.skip && *s.skip != 0; }
 
 struct Table {  // fd_optim_table with its types
     const uint64_t *params;
@@ -82,8 +100,9 @@ __global__ void __launch_bounds__(kThreads) optim_sumsq(Table T) {
     if (threadIdx.x == 0) T.partials[c] = s;
 }
 
-__global__ void __launch_bounds__(kThreads) optim_prepare(Table T, Hyper h, int clip) {
+__global__ void __launch_bounds__(kThreads) optim_prepare(Table T, HyperSource src, int clip) {
     __shared__ double lds[kWaves];
+    const Hyper h = load_hyper(src);
     if (clip) {
         double acc = 0.0;
         for (int c = threadIdx.x; c < T.n_chunks; c += kThreads) acc += T.partials[c];
@@ -99,6 +118,7 @@ __global__ void __launch_bounds__(kThreads) optim_prepare(Table T, Hyper h, int 
         T.norm[0] = 0.f;
         T.norm[1] = 1.f;
     }
+    if (skipped(src)) return;  // uniform; norm is written, step counts and coefficients stay
     for (int t = threadIdx.x; t < T.n_tensors; t += kThreads) {
         if (!(T.flags[t] & FD_OPTIM_HAS_GRAD)) continue;
         const int s = T.step[t] + 1;
@@ -163,7 +183,9 @@ __device__ __forceinline__ void step_chunk(float *__restrict__ p, const float *_
     }
 }
 
-__global__ void __launch_bounds__(kThreads) optim_step(Table T, Hyper h) {
+__global__ void __launch_bounds__(kThreads) optim_step(Table T, HyperSource src) {
+    if (skipped(src)) return;
+    const Hyper h = load_hyper(src);
     const int c = blockIdx.x;
     const int t = T.chunks[2 * c];
     if ((unsigned)t >= (unsigned)T.n_tensors) return;
@@ -240,13 +262,30 @@ extern "C" int fd_optim_adam_step(const fd_optim_table *table, double lr, double
     FD_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "fd_optim_adam_step: betas (%g, %g) must lie in [0, 1)", beta1, beta2);
     FD_REQUIRE(eps > 0.0, "fd_optim_adam_step: eps must be > 0");
     FD_REQUIRE(lr == lr && wd == wd && max_norm == max_norm, "fd_optim_adam_step: lr, wd or max_norm is NaN");
-    Hyper h;
-    h.lr = lr; h.beta1 = beta1; h.beta2 = beta2; h.eps = eps; h.wd = wd; h.max_norm = max_norm;
+    HyperSource src{};
+    src.h.lr = lr; src.h.beta1 = beta1; src.h.beta2 = beta2; src.h.eps = eps; src.h.wd = wd; src.h.max_norm = max_norm;
     hipStream_t st = fd::as_stream(stream_);
     const int clip = max_norm > 0.0 ? 1 : 0;
     const dim3 grid((unsigned)T.n_chunks), block(kThreads);
     if (clip) hipLaunchKernelGGL(optim_sumsq, grid, block, 0, st, T);
-    hipLaunchKernelGGL(optim_prepare, dim3(1), block, 0, st, T, h, clip);
-    hipLaunchKernelGGL(optim_step, grid, block, 0, st, T, h);
+    hipLaunchKernelGGL(optim_prepare, dim3(1), block, 0, st, T, src, clip);
+    hipLaunchKernelGGL(optim_step, grid, block, 0, st, T, src);
     return fd::check_launch("fd_optim_adam_step");
+}
+
+extern "C" int fd_optim_adam_step_dev(const fd_optim_table *table, const double *hyper, int clip, const int32_t *skip, fd_stream_t stream_) {
+    Table T;
+    if (int rc = make_table("fd_optim_adam_step_dev", table, T)) return rc;
+    FD_REQUIRE(hyper, "fd_optim_adam_step_dev: null hyper record");
+    FD_REQUIRE(((uintptr_t)hyper & 7) == 0, "fd_optim_adam_step_dev: the hyper record must be 8-byte aligned");
+    FD_REQUIRE(clip == 0 || clip == 1, "fd_optim_adam_step_dev: clip must be 0 or 1 (got %d)", clip);
+    HyperSource src{};
+    src.dev = hyper;
+    src.skip = skip;
+    hipStream_t st = fd::as_stream(stream_);
+    const dim3 grid((unsigned)T.n_chunks), block(kThreads);
+    if (clip) hipLaunchKernelGGL(optim_sumsq, grid, block, 0, st, T);
+    hipLaunchKernelGGL(optim_prepare, dim3(1), block, 0, st, T, src, clip);
+    hipLaunchKernelGGL(optim_step, grid, block, 0, st, T, src);
+    return fd::check_launch("fd_optim_adam_step_dev");
 }

@@ -262,6 +262,51 @@ class VoxelNet(SingleStageDetector):
         return out
 
 
+    def forward_points_train(self, clouds, voxel_cfg, example, counts=None, static=False, row_caps=None):
+        """The training twin of forward_points: device clouds -> fused voxeliser with mean features (the TRAIN cap max_voxel_num[0]) ->
+        index pyramid -> rows in index order -> backbone.forward_static_train -> neck -> head -> bbox_head.loss(example, preds).  Train mode
+        with gradients on; ``example`` is the TargetAssigner's output (hm / ind / mask / cat / anno_box).  ``counts``: per cloud a device
+        int32[1] with its number of valid rows.  ``static=True``: no host read anywhere -- the sparse levels are sized by ``row_caps`` (or the
+        data-free bounds) and every kernel takes its count from the device, so the call is issued without waiting for the device
+        (solver.StaticTrainStep); an overflowing level is detectable from ``last_level_counts`` and not computed correctly.
+        ``static=False``: ONE host read of the level counts sizes the levels exactly; it gives the same bits (bias gradients of the block
+        convolutions: to the last rounding).  Needs backbone.fused_bn; the loss runs without synchronisation with bbox_head.fused_loss."""
+        if not self.training or not torch.is_grad_enabled():
+            raise RuntimeError("forward_points_train is the training path: call .train() and enable gradients")
+        if getattr(self.bbox_head, "bev_map", False):
+            raise NotImplementedError("forward_points_train: a bev_map head takes a second input that this path does not carry")
+        dev = clouds[0].device
+        B = len(clouds)
+        rng, vs = voxel_cfg["range"], voxel_cfg["voxel_size"]
+        mv = voxel_cfg["max_voxel_num"]
+        max_voxels = int(mv[0] if isinstance(mv, (list, tuple)) else mv)  # train cap (preprocess.py:256-258)
+        max_points = int(voxel_cfg["max_points_in_voxel"])
+        cpad = sparse.pad_channels(clouds[0].shape[1])
+        mean = torch.empty((B * max_voxels, cpad), dtype=torch.float32, device=dev)
+        coors = torch.empty((B * max_voxels, 4), dtype=torch.int32, device=dev)
+        npts = torch.empty((B * max_voxels,), dtype=torch.int32, device=dev)
+        nvox = torch.empty((B,), dtype=torch.int32, device=dev)
+        for b, pts in enumerate(clouds):
+            sl = slice(b * max_voxels, (b + 1) * max_voxels)
+            hip_ops.voxelize(pts, vs, rng, max_points, max_voxels, batch_idx=b, want_voxels=False, want_mean=True,
+                             out=dict(mean=mean[sl], coors=coors[sl], num_points=npts[sl], num_voxels=nvox[b:b + 1]),
+                             n_points_dev=None if counts is None else counts[b])
+        grid = np.round((np.array(rng[3:], np.float32) - np.array(rng[:3], np.float32)) / np.array(vs, np.float32)).astype(np.int64)
+        bb = self.backbone
+        idx = bb.build_indexes(None, B, list(grid), dev, voxels=(coors, nvox, max_voxels), static=static, row_caps=row_caps)
+        self.__dict__["last_level_counts"] = idx[0].level_counts if static else [ix.n for ix in idx]
+        i0 = idx[0]
+        # zeros: a static level 0 has more rows than voxels, and the rows behind the count stay out of every sum only because no table names them
+        feats0 = torch.zeros((max(i0.n, 1), cpad), dtype=torch.float32, device=dev)[: i0.n]
+        for b in range(B if i0.n > 0 else 0):
+            sl = slice(b * max_voxels, (b + 1) * max_voxels)
+            hip_ops.rows_place(i0, coors[sl], mean[sl], cpad, torch.float32, n_dev=nvox[b:b + 1], out=feats0)
+        x = bb.forward_static_train(feats0, idx)
+        x = self.neck(x)
+        preds = self.bbox_head(x, None)
+        return self.bbox_head.loss(example, preds)
+
+
 class StaticStep(object):
     """One whole sweep -- voxelizer, index pyramid, rulebooks, 21 sparse convolutions, RPN, CenterHead, decode, rotated NMS --
     as ONE hipGraph replay with no host read-back in between.  Shapes are static: the clouds live in a

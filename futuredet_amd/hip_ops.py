@@ -196,6 +196,10 @@ class SparseIndex(object):
         nbr.n_out = out_index.n
         nbr.n_dev = out_index.n_dev if static else None
         nbr.n_expected = out_index.n_expected if static else 0
+        # the INPUT level's count: what the transposed table of a strided layer's input gradient runs on
+        src_static = getattr(self, "static", False)
+        nbr.n_in_dev = self.n_dev if src_static else None
+        nbr.n_in_expected = self.n_expected if src_static else 0
         return nbr
 
 
@@ -1224,6 +1228,62 @@ def optim_adam_step(table, lr, beta1, beta2, eps, wd, max_norm=0.0):
     Adam for every tensor, in at most three launches.  No allocation, no synchronisation."""
     check(_lib.load().fd_optim_adam_step(ctypes.byref(table.c_struct), float(lr), float(beta1), float(beta2), float(eps), float(wd), float(max_norm),
                                          _stream()), "fd_optim_adam_step")
+
+
+HYPER_FIELDS = ("lr", "beta1", "beta2", "eps", "wd", "max_norm")  # the device record of fd_optim_adam_step_dev, in this order
+
+
+def check_hyper(lr, beta1, beta2, eps, wd, max_norm):
+    """What fd_optim_adam_step refuses on the host, for values that travel through device memory: -> the six python floats"""
+    v = [float(x) for x in (lr, beta1, beta2, eps, wd, max_norm)]
+    if not (0.0 <= v[1] < 1.0 and 0.0 <= v[2] < 1.0):
+        raise ValueError("optimiser hyper-parameters: betas (%g, %g) must lie in [0, 1)" % (v[1], v[2]))
+    if not v[3] > 0.0:
+        raise ValueError("optimiser hyper-parameters: eps must be > 0 (got %g)" % v[3])
+    if v[0] != v[0] or v[4] != v[4] or v[5] != v[5]:
+        raise ValueError("optimiser hyper-parameters: lr, wd or max_norm is NaN")
+    return v
+
+
+def optim_adam_step_dev(table, hyper, clip, skip=None):
+    """fd_optim_adam_step_dev on an AdamTable: ``hyper`` float64 [6] on the device (HYPER_FIELDS; validate with check_hyper before the
+    upload), ``clip`` a host bool (it fixes the launch count), ``skip`` int32 [1] on the device or None.  No allocation, no
+    synchronisation; the same bits as optim_adam_step for the same six values."""
+    hyper = _dev(hyper, "hyper", torch.float64)
+    if hyper.numel() != len(HYPER_FIELDS):
+        raise FutureDetHipError("hyper must hold %d doubles (%s), got %d" % (len(HYPER_FIELDS), ", ".join(HYPER_FIELDS), hyper.numel()))
+    if skip is not None:
+        _dev(skip, "skip", torch.int32)
+    check(_lib.load().fd_optim_adam_step_dev(ctypes.byref(table.c_struct), _p(hyper), int(bool(clip)), _p(skip), _stream()), "fd_optim_adam_step_dev")
+
+
+def rows_colsum_chunk():
+    return int(_lib.load().fd_rows_colsum_chunk())
+
+
+def rows_colsum(x, n_dev=None):
+    """fd_rows_colsum: fp32 [C] = the sum of the first min(n, n_dev[0]) rows of x [n, C] (fp32 or bf16; n_dev None: all rows), summed in
+    double in a fixed order.  The rows behind the count are never read."""
+    L = _lib.load()
+    x = _dev(x, "x")
+    if x.dtype not in _DT or x.dim() != 2:
+        raise FutureDetHipError("rows_colsum: x must be a float32 or bfloat16 [n, C] tensor (got %s %s)" % (tuple(x.shape), x.dtype))
+    n, c = x.shape
+    out = torch.empty((c,), dtype=torch.float32, device=x.device)
+    ws = workspace.get("rows_colsum", L.fd_rows_colsum_workspace_bytes(n, c), x.device)
+    check(L.fd_rows_colsum(_p(x) if n else None, n, _p(n_dev), c, _DT[x.dtype], _p(out), _p(ws), ws.numel(), _stream()), "fd_rows_colsum")
+    return out
+
+
+def levels_overflow(counts, caps, flag=None):
+    """fd_levels_overflow: flag[0] (int32 on the device) = any counts[l] > caps[l]; counts / caps int32 device tensors of one length"""
+    counts, caps = _dev(counts, "counts", torch.int32), _dev(caps, "caps", torch.int32)
+    if counts.numel() != caps.numel():
+        raise FutureDetHipError("levels_overflow: %d counts, %d capacities" % (counts.numel(), caps.numel()))
+    if flag is None:
+        flag = torch.empty((1,), dtype=torch.int32, device=counts.device)
+    check(_lib.load().fd_levels_overflow(_p(counts), _p(caps), counts.numel(), _p(_dev(flag, "flag", torch.int32)), _stream()), "fd_levels_overflow")
+    return flag
 
 
 # ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------

@@ -176,6 +176,11 @@ SIGNATURES = {
     "fd_optim_chunk": (c_int, []),
     "fd_optim_zero_grad": (c_int, [ctypes.POINTER(OptimTable), c_void_p]),
     "fd_optim_adam_step": (c_int, [ctypes.POINTER(OptimTable)] + [ctypes.c_double] * 6 + [c_void_p]),
+    "fd_optim_adam_step_dev": (c_int, [ctypes.POINTER(OptimTable), c_void_p, c_int, c_void_p, c_void_p]),
+    "fd_rows_colsum_chunk": (c_int, []),
+    "fd_rows_colsum_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "fd_rows_colsum": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_levels_overflow": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fd_loss_chunk": (c_int, []),
     "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),

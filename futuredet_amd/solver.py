@@ -203,11 +203,13 @@ class FusedAdam(object):
         hip_ops.optim_zero_grad(self._table)
         self._attach()
 
-    def step(self, grad_clip=None):
-        """Decay, clip (``grad_clip`` = dict(max_norm=..., norm_type=2) or None) and Adam with the current lr / mom.  Returns the
-        device tensor of total_norm when clipping is on.  A ``p.grad`` that is no longer the attached view is copied into it; None
-        means no gradient this step: the tensor is decayed, its moments and step count stay."""
-        max_norm = parse_grad_clip(grad_clip)
+    def hyper_values(self, grad_clip=None):
+        """The six scalars of a step with the current lr / mom, validated: [lr, beta1, beta2, eps, wd, max_norm] (hip_ops.HYPER_FIELDS) --
+        what a caller uploads into the device record of ``step(hyper=...)``."""
+        return hip_ops.check_hyper(self._lr, self._mom, self._beta, self._eps, self._wd, parse_grad_clip(grad_clip))
+
+    def _gather_gradients(self):
+        """The table with this step's pointers, gradients and has-gradient flags in place (uploads only what changed)."""
         tab = self._table
         tab.sync_pointers()
         has_grad = []
@@ -220,6 +222,29 @@ class FusedAdam(object):
                     v.copy_(g)
                 has_grad.append(g is not None)
         tab.set_has_grad(has_grad)
+        return tab
+
+    def _step_dev(self, grad_clip, hyper, skip):
+        clip = parse_grad_clip(grad_clip) > 0.0
+        tab = self._gather_gradients()
+        hip_ops.optim_adam_step_dev(tab, hyper, clip, skip)
+        torch.autograd.graph.increment_version(tab.params)
+        return tab.norm[0].clone() if clip else None
+
+    def step(self, grad_clip=None, hyper=None, skip=None):
+        """Decay, clip (``grad_clip`` = dict(max_norm=..., norm_type=2) or None) and Adam with the current lr / mom.  Returns the
+        device tensor of total_norm when clipping is on.  A ``p.grad`` that is no longer the attached view is copied into it; None
+        means no gradient this step: the tensor is decayed, its moments and step count stay.
+        ``hyper`` (float64 [6] on the device, the values of ``hyper_values``): the step reads its scalars from that record when it
+        RUNS, not when it is issued (fd_optim_adam_step_dev) -- a captured step follows the schedule; ``grad_clip`` still decides
+        whether the norm is computed, its max_norm comes from the record.  ``skip`` (int32 [1] on the device): non-zero leaves
+        parameters, moments and step counts as they are.  Without ``hyper`` the call is the one it always was."""
+        if hyper is not None:
+            return self._step_dev(grad_clip, hyper, skip)
+        if skip is not None:
+            raise ValueError("FusedAdam.step: skip needs the device record (hyper=...)")
+        max_norm = parse_grad_clip(grad_clip)
+        tab = self._gather_gradients()
         hip_ops.optim_adam_step(tab, self._lr, self._mom, self._beta, self._eps, self._wd, max_norm)
         # the kernel wrote through raw pointers: weights_version (folded / packed weight caches, captured graphs) looks at _version
         torch.autograd.graph.increment_version(tab.params)
@@ -309,5 +334,232 @@ def train_steps(model, batches, optimizer, scheduler, grad_clip=None, start_iter
         yield losses
 
 
+class StaticTrainStep(object):
+    """One whole training iteration of a VoxelNet -- zero_grad, voxeliser, index pyramid, AssignLabel's targets, sparse backbone, RPN,
+    CenterHead, loss, backward, clipping and Adam -- issued without ever waiting for the device: detectors.StaticStep's counterpart for
+    training, without its graph (see ``graph`` below).  Shapes are static: the clouds live in fixed-capacity buffers with
+    their row counts on the device, the ground truth is padded to [B, T, max_gt, 12], the sparse levels are sized by row capacities
+    and every kernel takes its count from device memory (VoxelNet.forward_points_train(static=True)); lr, beta1 and the other four
+    scalars of the optimiser reach the kernels through a device record that is refreshed before every step
+    (FusedAdam.step(hyper=...)): the launches do not bake the schedule in.
+
+        step = StaticTrainStep(model, cfg.voxel_generator, assigner, optimizer, scheduler, grad_clip, capacity=400000, batch_size=2)
+        step.warm_up(batches)                 # eager steps: conv plan choices + level counts; leaves model and optimiser as they were
+        for batch in loader:                  # batch: dict(clouds=[B device tensors [N_i, ndim]], gt_boxes=[B, T, n, 12] fp32,
+            losses = step(batch)              #             gt_counts=[B, T] int32, gt_classes=[B, T, n] int32[, gt_trajectory])
+
+    ``step(batch)`` runs scheduler.step(iteration), uploads the six scalars, copies the batch into the static inputs and issues the
+    launches.  It returns the model's loss dict (device tensors) with ``total_norm`` when clipping is on.
+
+    Row capacities (``row_caps="auto"``): ``headroom`` x the largest level counts of the warm-up batches + 4096.  A batch that needs
+    more rows on some level sets a flag ON THE DEVICE (fd_levels_overflow) that makes the optimiser step of that iteration a no-op:
+    parameters, moments and step counts stay.  With ``check=True`` (default) the level counts are read back after the step -- the one
+    synchronisation of the call -- and an overflowed batch is re-run on the host-sized path (forward_points_train(static=False))
+    with the same scheduler iteration, so step counts and the iteration advance exactly once.  ``check=False`` keeps the call
+    asynchronous; ask ``overflowed()`` later.  What an overflowed step leaves behind: the BatchNorm running statistics (and
+    num_batches_tracked) were updated once by its forward pass, on a truncated but valid batch, before the re-run updates them again.
+
+    ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
+    device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward
+    included -- crashed the HIP runtime when the capture was ended (torch 2.10 on ROCm 7, MI355X; DESIGN.md "The sync-free training
+    step"), so the capture is not part of the class; ``graph=True`` raises NotImplementedError.  One StaticTrainStep belongs to one stream."""
+
+    def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
+                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False):
+        from .detectors import VoxelNet
+
+        if not isinstance(model, VoxelNet):
+            raise NotImplementedError("StaticTrainStep: %s is not a VoxelNet; the static training step covers the sparse-backbone detector "
+                                      "only (PointPillars trains through train_steps)" % type(model).__name__)
+        head, bb = model.bbox_head, model.backbone
+        if getattr(head, "dcn_head", False):
+            raise NotImplementedError("StaticTrainStep: a dcn_head CenterHead is not covered (dcn_head=True); train it through train_steps")
+        if not getattr(bb, "fused_bn", False):
+            raise ValueError("StaticTrainStep: backbone.fused_bn is off; torch's BatchNorm1d cannot take its row count from the device "
+                             "(set model.backbone.fused_bn = True)")
+        if not getattr(head, "fused_loss", False):
+            raise ValueError("StaticTrainStep: bbox_head.fused_loss is off; the torch loss copies its terms to the host "
+                             "(set model.bbox_head.fused_loss = True)")
+        if getattr(head, "bev_map", False):
+            raise NotImplementedError("StaticTrainStep: a bev_map head takes a second input that the step does not carry")
+        self.model, self.voxel_cfg, self.assigner, self.optimizer, self.scheduler = model, voxel_cfg, assigner, optimizer, scheduler
+        if graph:
+            raise NotImplementedError("StaticTrainStep: graph=True is not available -- ending the capture of the whole step crashed the HIP "
+                                      "runtime; the step is issued eagerly without host synchronisation (graph=False)")
+        self.grad_clip = grad_clip
+        parse_grad_clip(grad_clip)
+        self.row_caps_mode, self.headroom = row_caps, float(headroom)
+        self.B, self.capacity, self.ndim = int(batch_size), int(capacity), int(ndim)
+        self.T = int(timesteps if timesteps is not None else getattr(head, "timesteps", 1))
+        self.max_gt = int(max_gt if max_gt is not None else assigner.max_objs)
+        dev = next(model.parameters()).device
+        self.device = dev
+        B, T, n = self.B, self.T, self.max_gt
+        self.points = torch.zeros((B, self.capacity, self.ndim), dtype=torch.float32, device=dev)
+        self.counts = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self.gt_boxes = torch.zeros((B, T, n, 12), dtype=torch.float32, device=dev)
+        self.gt_counts = torch.zeros((B, T), dtype=torch.int32, device=dev)
+        self.gt_classes = torch.zeros((B, T, n), dtype=torch.int32, device=dev)
+        self.gt_trajectory = torch.zeros((B, T, n), dtype=torch.int32, device=dev) if assigner.extra_sets else None
+        self.targets = assigner.outputs(B, T, dev)
+        self.hyper = torch.zeros((len(hip_ops.HYPER_FIELDS),), dtype=torch.float64, device=dev)
+        self.skip = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._ring, self._slot = None, 0
+        self.iteration = 0
+        self.expected, self.caps, self.caps_dev = None, None, None
+        self.outputs, self.level_counts = None, None
+
+    def __del__(self):
+        try:
+            hip_ops.workspace.release(id(self))
+        except Exception:
+            pass
+
+    def reset(self):
+        """drops the row capacities (the next call derives them again from ``row_caps`` and the warm-up counts)"""
+        self.caps, self.caps_dev, self.outputs = None, None, None
+
+    # -- inputs
+    def _pinned(self):
+        """a slot of the ring of pinned staging buffers (cloud counts, the six scalars), free again once its last copy has run"""
+        if self._ring is None:
+            self._ring = [[torch.empty((self.B,), dtype=torch.int32).pin_memory(), torch.empty((6,), dtype=torch.float64).pin_memory(), None]
+                          for _ in range(8)]
+        slot = self._ring[self._slot % len(self._ring)]
+        self._slot += 1
+        if slot[2] is not None and not slot[2].query():
+            slot[2].synchronize()  # (only when the stream is eight steps behind the host)
+        return slot
+
+    def _load(self, batch, iteration):
+        clouds = batch["clouds"]
+        if len(clouds) != self.B:
+            raise ValueError("the step was built for batches of %d clouds, got %d" % (self.B, len(clouds)))
+        if self.scheduler is not None:
+            self.scheduler.step(iteration)
+        slot = self._pinned()
+        counts_host, hyper_host = slot[0], slot[1]
+        hyper_host.numpy()[:] = self.optimizer.hyper_values(self.grad_clip)
+        for b, c in enumerate(clouds):
+            n = int(c.shape[0])
+            if n > self.capacity or c.shape[1] != self.ndim:
+                raise ValueError("cloud of %d x %d rows does not fit the step's %d x %d buffer" % (n, c.shape[1], self.capacity, self.ndim))
+            self.points[b, :n].copy_(c, non_blocking=True)
+            counts_host[b] = n
+        self.counts.copy_(counts_host, non_blocking=True)
+        self.hyper.copy_(hyper_host, non_blocking=True)
+        slot[2] = torch.cuda.Event()
+        slot[2].record()
+        boxes, gcounts, classes = batch["gt_boxes"], batch["gt_counts"], batch["gt_classes"]
+        n = int(boxes.shape[2])
+        if tuple(boxes.shape[:2]) != (self.B, self.T) or n > self.max_gt or boxes.shape[3] != 12:
+            raise ValueError("gt_boxes %s do not fit the step's [%d, %d, <= %d, 12] buffer" % (tuple(boxes.shape), self.B, self.T, self.max_gt))
+        self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
+        self.gt_counts.copy_(gcounts, non_blocking=True)
+        self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
+        if self.gt_trajectory is not None:
+            self.gt_trajectory[:, :, :n].copy_(batch["gt_trajectory"], non_blocking=True)
+
+    # -- the step
+    def _body(self, static):
+        """every launch of one iteration, in order, on the current stream; nothing in it waits for the device when ``static``"""
+        m, opt = self.model, self.optimizer
+        if not m.training:
+            m.train()
+        opt.zero_grad()
+        example = self.assigner(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_trajectory, out=self.targets, check=False)
+        clouds = [self.points[b] for b in range(self.B)]
+        counts = [self.counts[b:b + 1] for b in range(self.B)]
+        losses = m.forward_points_train(clouds, self.voxel_cfg, example, counts=counts, static=static, row_caps=self.caps if static else None)
+        level_counts = m.last_level_counts
+        guarded = static and self.caps_dev is not None
+        if guarded:
+            hip_ops.levels_overflow(level_counts, self.caps_dev, self.skip)
+        sum(losses["loss"]).backward()
+        total_norm = opt.step(grad_clip=self.grad_clip, hyper=self.hyper, skip=self.skip if guarded else None)
+        losses = dict(losses)
+        if total_norm is not None:
+            losses["total_norm"] = total_norm
+        return losses, level_counts
+
+    def _run_static(self):
+        with hip_ops.workspace.scope(id(self)):  # scratch of its own, whatever stream the step is issued on
+            return self._body(True)
+
+    def _state(self):
+        """every tensor a step changes: parameters and buffers of the model, the optimiser's moments and step counts"""
+        tab = self.optimizer._table
+        return list(self.model.state_dict(keep_vars=True).values()) + [tab.exp_avg, tab.exp_avg_sq, tab.step]
+
+    def _restoring(self):
+        """context: the model, the optimiser and its scheduled lr / mom leave as they came (warm-up steps are not training)"""
+        step = self
+
+        class _Restore(object):
+            def __enter__(self_):
+                self_.saved = [t.detach().clone() for t in step._state()]
+                self_.lr_mom = (step.optimizer.lr, step.optimizer.mom)
+
+            def __exit__(self_, *exc):
+                with torch.no_grad():
+                    for t, s in zip(step._state(), self_.saved):
+                        t.detach().copy_(s)
+                step.optimizer.lr, step.optimizer.mom = self_.lr_mom
+
+        return _Restore()
+
+    def warm_up(self, batches):
+        """Eager steps on the host-sized path (forward_points_train(static=False)) over representative batches: lets the dense
+        convolutions pick their kernels, fixes the optimiser's gradient set and pointer table, and records the largest level counts
+        (the capacities of row_caps="auto").  The model, the optimiser and the iteration count are restored afterwards."""
+        seen = None
+        with self._restoring():
+            for batch in batches:
+                self._load(batch, self.iteration)
+                self._body(False)
+                counts = [int(v) for v in self.model.last_level_counts]
+                seen = counts if seen is None else [max(a, b) for a, b in zip(seen, counts)]
+        if seen is None:
+            raise ValueError("StaticTrainStep.warm_up needs at least one batch")
+        self.expected = seen
+        self.reset()
+
+    def _set_caps(self):
+        mv = self.voxel_cfg["max_voxel_num"]
+        cap0 = self.B * int(mv[0] if isinstance(mv, (list, tuple)) else mv)
+        if self.row_caps_mode == "datafree":
+            self.caps, self.caps_dev = None, None
+            return
+        if self.row_caps_mode == "auto":
+            if self.expected is None:
+                raise RuntimeError("StaticTrainStep.warm_up(batches) must run before the first step (row_caps=\"auto\")")
+            self.caps = [cap0] + [int(self.headroom * e) + 4096 for e in self.expected[1:]]  # (level 0 is capped by the voxeliser itself)
+        else:
+            self.caps = [int(c) for c in self.row_caps_mode]
+        if self.model.backbone.train_dtype == torch.float32 and max(self.caps[1:]) >= (1 << 23):
+            raise NotImplementedError("StaticTrainStep: a sparse level with a row capacity >= 2^23 (fp32 kernel limit); use a smaller batch")
+        self.caps_dev = torch.tensor(self.caps, dtype=torch.int32).to(self.device)
+
+    def __call__(self, batch, check=True):
+        """One iteration on ``batch`` (see the class).  ``check``: read the level counts back after the step and re-run an overflowed
+        batch on the host-sized path -- one synchronisation, at the end."""
+        if self.caps is None and self.row_caps_mode != "datafree":  # first call, or after warm_up() / reset()
+            self._set_caps()
+        self._load(batch, self.iteration)
+        self.outputs, self.level_counts = self._run_static()
+        if check and self.caps is not None and self.overflowed():
+            self.outputs, _ = self._body(False)  # the device skipped the update; same record of scalars, same iteration
+        self.iteration += 1
+        return self.outputs
+
+    def overflowed(self, level_counts_host=None):
+        """True when the last step needed more rows on some level than its capacities: the device has skipped its optimiser update and
+        the batch has to be run again (``step(batch)`` with check=True does).  Synchronises unless the counts are passed in."""
+        if self.caps is None or self.level_counts is None:
+            return False
+        lc = self.level_counts.cpu().tolist() if level_counts_host is None else [int(v) for v in level_counts_host]
+        return any(n > c for n, c in zip(lc, self.caps))
+
+
 __all__ = ["FusedAdam", "OneCycle", "LRSchedulerStep", "annealing_cos", "parameter_groups", "parse_grad_clip", "build_one_cycle_optimizer",
-           "create_learning_rate_scheduler", "train_steps"]
+           "create_learning_rate_scheduler", "train_steps", "StaticTrainStep"]

@@ -168,12 +168,17 @@ class _SparseConvFunction(torch.autograd.Function):
                 inv = getattr(nbr, "inv", None)  # cached with the rulebook (indice_key)
                 if inv is None:
                     inv = nbr.inv = hip_ops.rulebook_transpose(nbr, n_out, n_in)
+                    if getattr(nbr, "n_in_dev", None) is not None:  # static indexes: dX has the INPUT level's rows, n_in is their capacity
+                        inv.n_dev, inv.n_expected = nbr.n_in_dev, nbr.n_in_expected
                 wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_TRANSPOSED, dt)
                 dx = hip_ops.spconv_apply(dy, wt, None, inv, n_in, cin_p)
         if ctx.needs_input_grad[1]:
             dw = hip_ops.spconv_wgrad(feats, dy, nbr, n_out)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy[:n_out].sum(0) if dt == torch.float32 else dy[:n_out].float().sum(0)
+            if getattr(nbr, "n_dev", None) is not None:  # the count lives on the device; the rows behind it are uninitialised memory
+                db = hip_ops.rows_colsum(dy[:n_out], nbr.n_dev)
+            else:
+                db = dy[:n_out].sum(0) if dt == torch.float32 else dy[:n_out].float().sum(0)
         return dx, dw, db, None, None, None
 
 
@@ -185,14 +190,14 @@ class _SparseBatchNormFunction(torch.autograd.Function):
     statistics are fp32.  On bf16 rows no fp32 [n, C] tensor exists at any point."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, bn, relu):
+    def forward(ctx, x, gamma, beta, residual, bn, relu, n_dev=None):
         y, saved = hip_ops.sparse_bn_train_forward(x, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps,
-                                                   bn.momentum, residual=residual, relu=relu)
+                                                   bn.momentum, residual=residual, relu=relu, n_dev=n_dev)
         # the kernel wrote through raw pointers: packed_weight keys the eval path's folded-BN cache on these counters
         for buf in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
             torch.autograd.graph.increment_version(buf)
         ctx.save_for_backward(x, y, gamma, saved)
-        ctx.relu = relu
+        ctx.relu, ctx.n_dev = relu, n_dev
         return y
 
     @staticmethod
@@ -201,8 +206,8 @@ class _SparseBatchNormFunction(torch.autograd.Function):
         x, y, gamma, saved = ctx.saved_tensors
         want_res = ctx.needs_input_grad[3]
         dx, dres, dgamma, dbeta = hip_ops.sparse_bn_train_backward(dy.to(x.dtype).contiguous(), x, y, gamma, saved, relu=ctx.relu,
-                                                                   want_residual=want_res)
-        return dx, dgamma, dbeta, dres, None, None
+                                                                   want_residual=want_res, n_dev=ctx.n_dev)
+        return dx, dgamma, dbeta, dres, None, None, None
 
 
 def batch_norm_fusable(features, bn):
@@ -215,16 +220,20 @@ def batch_norm_fusable(features, bn):
             and features.shape[0] >= 2 and hip_ops.sparse_bn_channels_ok(features.shape[1]))
 
 
-def batch_norm_act(features, bn, residual=None, relu=True):
+def batch_norm_act(features, bn, residual=None, relu=True, n_dev=None):
     """relu(bn(features) [+ residual]) in training mode on the fused kernels; ``bn`` is the existing nn.BatchNorm1d module (parameters,
-    buffers and state-dict keys unchanged).  Raises where batch_norm_fusable(features, bn) does not hold: there is no fallback here."""
+    buffers and state-dict keys unchanged).  Raises where batch_norm_fusable(features, bn) does not hold: there is no fallback here.
+    ``n_dev`` (int32 [1] on the device): the valid row count of static indexes -- features.shape[0] is then the row capacity; both
+    directions take their statistics over the counted rows and write zeros behind them."""
     if not batch_norm_fusable(features, bn):
         raise hip_ops.FutureDetHipError("batch_norm_act: needs a training-mode affine BatchNorm1d with running statistics and a momentum, "
                                         "gradients enabled and fp32 or bf16 device features [n >= 2, C], C a multiple of 16 up to 128 (got %s %s)"
                                         % (tuple(features.shape), features.dtype))
     if residual is not None:
         residual = residual.to(features.dtype).contiguous()
-    return _SparseBatchNormFunction.apply(features.contiguous(), bn.weight, bn.bias, residual, bn, bool(relu))
+    if n_dev is None:  # (the call as it always was)
+        return _SparseBatchNormFunction.apply(features.contiguous(), bn.weight, bn.bias, residual, bn, bool(relu))
+    return _SparseBatchNormFunction.apply(features.contiguous(), bn.weight, bn.bias, residual, bn, bool(relu), n_dev)
 
 
 class SparseConvolution(SparseModule):

@@ -641,6 +641,35 @@ int fd_optim_chunk(void);
 int fd_optim_zero_grad(const fd_optim_table *table, fd_stream_t stream);
 int fd_optim_adam_step(const fd_optim_table *table, double lr, double beta1, double beta2, double eps, double wd, double max_norm,
                        fd_stream_t stream);
+/* fd_optim_adam_step_dev: the same kernels with the six scalars read from DEVICE memory at run time -- hyper[0..5] = lr, beta1, beta2,
+ * eps, wd, max_norm (doubles, 8-byte aligned) -- so a launch captured into a graph follows a schedule that changes lr and beta1 at every
+ * iteration.  Given the same six values it writes the same bits as fd_optim_adam_step (parameters, both moments, step, coef, norm):
+ * both hand the kernels the same doubles.  clip (0 or 1) is a host argument because it fixes the launch count (1: three launches,
+ * hyper[5] is max_norm; 0: two launches, norm = (0, 1), hyper[5] is not read).  skip (device int32[1], may be NULL): when non-zero at run
+ * time the call changes nothing but norm (and the partials scratch): no decay, no moments, no step counts, no parameter update.
+ * Host validation: the table as above, a null or misaligned hyper, clip not 0 or 1 are FD_EINVAL; the VALUES of the record cannot be
+ * checked on the host -- the caller validates them before it uploads them (betas in [0, 1), eps > 0, no NaN). */
+int fd_optim_adam_step_dev(const fd_optim_table *table, const double *hyper, int clip, const int32_t *skip, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Training: two small pieces of a step that never waits for the host (fd_rows.hip).  Purely additive: fd_abi_version() stays 8.
+ * fd_rows_colsum: out[c] (fp32 [C]) = the sum over the first min(n, max(*n_dev, 0)) rows (n_dev NULL: n rows) of the row-major
+ *   contiguous x [n, C], dtype 0 = fp32 rows, 1 = bf16 rows (widened exactly).  Rows at or behind the count are never read (they may
+ *   be uninitialised).  C in {16, 32, 64, 128}; n in [0, 2^30]; n = 0 or a count of 0 gives zeros.  Rows are cut into chunks of
+ *   fd_rows_colsum_chunk() (= FD_ROWS_COLSUM_CHUNK) rows; a chunk's 256 / C row lanes add their rows in row order and are added in lane
+ *   order, the chunk partials likewise; all in double, rounded to fp32 once.  No atomics: the same bits on every run, and they depend
+ *   on the count and C only, not on the capacity n.  Two launches (one for n = 0); no allocation, no synchronisation.
+ *   workspace >= fd_rows_colsum_workspace_bytes(n, C) (0 = invalid sizes), 16-byte aligned.  FD_EINVAL for: an unsupported C or dtype,
+ *   n out of range, null out, null x with n > 0, a workspace that is null, misaligned or too small.
+ * fd_levels_overflow: one launch; flag[0] = 1 if counts[l] > caps[l] for any l < n_levels, else 0 (all three in device memory, int32;
+ *   n_levels in [1, 64]).  FD_EINVAL for a null pointer or n_levels out of range.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_ROWS_COLSUM_CHUNK 512
+int fd_rows_colsum_chunk(void);
+size_t fd_rows_colsum_workspace_bytes(int64_t n, int C);
+int fd_rows_colsum(const void *x, int64_t n, const int32_t *n_dev, int C, int dtype, float *out, void *workspace, size_t workspace_bytes,
+                   fd_stream_t stream);
+int fd_levels_overflow(const int32_t *counts, const int32_t *caps, int n_levels, int32_t *flag, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
