@@ -542,6 +542,50 @@ def conv2d_nhwc_bf16(x, wpk, bias, cout, ks, stride=1, relu=True, out=None, co_o
     return out
 
 
+def pack_conv2d_weight_device(w, transposed=False):
+    """[Cout, Cin, k, k] float32 on the device -> pack_conv2d_weight's bytes, packed on the device (fd_conv2d_pack_weight_dev: one
+    launch, no host round trip).  ``transposed``: the weights of the input gradient, w'[ci][co][k-1-ky][k-1-kx] = w[co][ci][ky][kx]
+    (a Cout -> Cin convolution; needs Cout % 32 == 0)."""
+    L = _lib.load()
+    w = _dev(w.detach(), "w", torch.float32)
+    if w.dim() != 4 or w.shape[2] != w.shape[3]:
+        raise FutureDetHipError("pack_conv2d_weight_device: need a [Cout, Cin, k, k] weight (got %s)" % (tuple(w.shape),))
+    cout, cin, ks, _ = w.shape
+    if transposed and cout % 32:
+        raise FutureDetHipError("pack_conv2d_weight_device: the transposed weights need Cout %% 32 == 0 (got %s)" % (tuple(w.shape),))
+    nbytes = L.fd_conv2d_packed_weight_bytes(cin, cout, ks) if transposed else L.fd_conv2d_packed_weight_bytes(cout, cin, ks)
+    if nbytes == 0:
+        raise FutureDetHipError("fd_conv2d: unsupported weight shape %s" % (tuple(w.shape),))
+    out = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+    check(L.fd_conv2d_pack_weight_dev(_p(w), cout, cin, ks, int(bool(transposed)), _p(out), _stream()), "fd_conv2d_pack_weight_dev")
+    return out
+
+
+def conv2d_wgrad_bf16_chunk():
+    """Pixels per partial of conv2d_wgrad_bf16: a constant of the library, part of its summation order."""
+    return int(_lib.load().fd_conv2d_wgrad_bf16_chunk())
+
+
+def conv2d_wgrad_bf16(x_nhwc, dy_nhwc, ks):
+    """Weight gradient of the stride-1 convolution y = conv(x, w) (padding 1 for ks 3, 0 for ks 1): x [B,H,W,Cin] and dy [B,H,W,Cout] bf16
+    contiguous -> dW [Cout, Cin, ks, ks] float32 (fd_conv2d_wgrad_bf16: deterministic, no atomics)."""
+    L = _lib.load()
+    x = _dev(x_nhwc, "x_nhwc", torch.bfloat16)
+    dy = _dev(dy_nhwc, "dy_nhwc", torch.bfloat16)
+    if x.dim() != 4 or dy.dim() != 4 or x.shape[:3] != dy.shape[:3]:
+        raise FutureDetHipError("conv2d_wgrad_bf16: x [B,H,W,Cin] and dy [B,H,W,Cout] must cover the same pixels (got %s and %s)"
+                                % (tuple(x.shape), tuple(dy.shape)))
+    B, H, W, cin = x.shape
+    cout = dy.shape[3]
+    nbytes = L.fd_conv2d_wgrad_bf16_workspace_bytes(B, H, W, cin, cout, ks)
+    if nbytes == 0:
+        raise FutureDetHipError("conv2d_wgrad_bf16: unsupported problem %s -> %d channels, ks %s" % (tuple(x.shape), cout, ks))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device)
+    check(L.fd_conv2d_wgrad_bf16(_p(x), _p(dy), B, H, W, cin, cout, ks, _p(ws), ws.numel(), _p(dw), _stream()), "fd_conv2d_wgrad_bf16")
+    return dw
+
+
 def pack_conv2d_weight_f32(w_oihw):
     """[Cout, Cin, k, k] float32 -> MFMA-fragment-ordered fp32 weights on the same device (fd_conv2d_f32_pack_weight)."""
     L = _lib.load()

@@ -162,6 +162,10 @@ SIGNATURES = {
     "fd_spconv_wgrad_bf16": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
     "fd_spconv_pack_weight_device_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fd_conv2d_pack_weight_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fd_conv2d_wgrad_bf16_chunk": (c_int, []),
+    "fd_conv2d_wgrad_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fd_conv2d_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "fd_dense_gather": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p]),
     "fd_pillar_train_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "fd_pillar_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_float, c_float, c_float,

@@ -3,7 +3,8 @@
 into the convolutions (ZeroPad2d merged into the conv padding) on the hand-written MFMA convolutions (dense_bf16.py:
 NHWC, bf16 or fp32, concat and transposed convolution written in place).  That plan is the ONLY eval-mode device path: a stack
 it cannot take (a channel count that is not a multiple of the kernels' granule) raises instead of running anywhere else.
-Training mode and host tensors (the CPU tests of the state-dict surface) run the plain nn.Module stack, forward_modules."""
+Training mode and host tensors (the CPU tests of the state-dict surface) run the plain nn.Module stack, forward_modules; with
+train_dtype = torch.bfloat16 a training-mode device map runs in mixed precision instead (forward_mixed, dense_train.py)."""
 import logging
 
 import numpy as np
@@ -56,6 +57,7 @@ class RPN(nn.Module):
         self.deblocks = nn.ModuleList(deblocks)
         self.compute_dtype = torch.float32
         self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the blocks and deblocks runs on fd_dense_bn.hip
+        self.train_dtype = torch.float32  # training: torch.bfloat16 = mixed precision on the bf16 NHWC convolutions (forward_mixed)
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
         (logger or logging.getLogger("RPN")).info("Finish RPN Initialization")
@@ -98,6 +100,25 @@ class RPN(nn.Module):
             x = torch.cat(ups, dim=1)
         return x
 
+    def forward_mixed(self, x):
+        """Training-mode forward in mixed precision (train_dtype = torch.bfloat16, device maps): the BEV map is converted once to bf16
+        channels-last, every block and deblock runs through dense_train.run_stack_bf16 -- the stride-1 3 x 3 convolutions and the
+        1 x 1 deblock on fd_conv2d_nhwc_bf16 / fd_conv2d_wgrad_bf16 with fp32 master weights and fp32 weight gradients, BatchNorm with fp32
+        statistics -- and the concatenated map is returned fp32 and NCHW-contiguous, which is what the head sees from forward_modules.
+        ``fused_bn`` has no effect here: fd_dense_bn.hip takes fp32 NCHW planes only (no NHWC / bf16 form yet), so BatchNorm2d runs the
+        backbone's un-fused recipe, bn(x.float()) + ReLU + one rounding."""
+        from .dense_train import run_stack_bf16
+
+        x = x.to(torch.bfloat16, memory_format=torch.channels_last)
+        ups = []
+        for i in range(len(self.blocks)):
+            x = run_stack_bf16(self.blocks[i], x)
+            if i >= self.first_up:
+                ups.append(run_stack_bf16(self.deblocks[i - self.first_up], x))
+        if len(ups) > 0:
+            x = torch.cat(ups, dim=1)
+        return x.to(torch.float32, memory_format=torch.contiguous_format)
+
     invalidate_caches = _drop_caches
 
     def _apply(self, fn, *a, **kw):  # .to() / .cuda() / .float(): derived weights live on the old device / dtype
@@ -105,6 +126,11 @@ class RPN(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     def forward(self, x):
+        if self.training:
+            if self.train_dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError("RPN: train_dtype must be torch.float32 or torch.bfloat16 (got %s)" % (self.train_dtype,))
+            if self.train_dtype == torch.bfloat16 and x.is_cuda:
+                return self.forward_mixed(x)
         if self.training or not x.is_cuda:
             return self.forward_modules(x)
         if self.compute_dtype not in (torch.bfloat16, torch.float32):

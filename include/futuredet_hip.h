@@ -527,6 +527,31 @@ int fd_spconv_wgrad_bf16(const void *in_feats, int64_t n_in, const void *dy, con
 int fd_spconv_pack_weight_device_bf16(const float *w_kio, int K, int cin, int cout, int mode, void *wpacked, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Mixed-precision training of the dense stride-1 convolutions (fd_conv2d_grad_bf16.hip): bf16 NHWC activations, fp32 master weights
+ * and gradients.  Purely additive: fd_abi_version() stays 8.  The forward is fd_conv2d_nhwc_bf16; the input gradient is
+ * fd_conv2d_nhwc_bf16 on dy with the mode-1 weights below (a cout -> cin convolution of the same kernel size and padding).
+ *   fd_conv2d_pack_weight_dev: replaces fd_conv2d_pack_weight (a host loop + upload, i.e. a synchronisation per step) in training.
+ *                     w_oihw [cout][cin][ks][ks] fp32 DEVICE memory, ks 1 or 3, cin % 32 == 0.  mode 0: byte for byte what
+ *                     fd_conv2d_pack_weight writes ([cout_pad/32][cin/32][tap][ksub][lane][8] bf16, the same round-to-nearest-even,
+ *                     zeros for co >= cout).  mode 1: the packed form of w'[ci][co][ks-1-ky][ks-1-kx] = w[co][ci][ky][kx], the
+ *                     cin' = cout, cout' = cin problem; needs cout % 32 == 0; fd_conv2d_packed_weight_bytes(cin, cout, ks) bytes.
+ *                     One launch, no host copy.
+ *   fd_conv2d_wgrad_bf16: replaces the fp32 NCHW weight gradient torch runs for these layers.  x [B,H,W,cin] bf16, dy [B,H,W,cout]
+ *                     bf16 (stride 1; padding 1 for ks 3, 0 for ks 1), cin and cout multiples of 32 -> dw [cout][cin][ks][ks] FP32
+ *                     (overwritten).  bf16 x bf16 products accumulated in fp32 on the matrix core.  The pixels, in (b, y, x) order,
+ *                     are cut into chunks of fd_conv2d_wgrad_bf16_chunk() (a constant of the library); one fp32 partial per (chunk,
+ *                     tap) goes to `workspace` (fd_conv2d_wgrad_bf16_workspace_bytes; 0 = bad arguments) and the partials are summed
+ *                     in chunk order: bit-identical from run to run, no atomics.  The workspace need not be initialised: every word
+ *                     that is read has been written by the same call.  Maps of 2^31 pixels and more: FD_EINVAL.  Neither allocates
+ *                     nor synchronises.
+ * ------------------------------------------------------------------------------------------------- */
+int fd_conv2d_pack_weight_dev(const float *w_oihw, int cout, int cin, int ks, int mode, void *wpacked, fd_stream_t stream);
+int fd_conv2d_wgrad_bf16_chunk(void);
+size_t fd_conv2d_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin, int cout, int ks);
+int fd_conv2d_wgrad_bf16(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, void *workspace,
+                         size_t workspace_bytes, float *dw, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training targets: AssignLabel's heat maps and box rows (fd_targets.hip) -- det3d/datasets/pipelines/preprocess.py:336-910
  * (NuScenesDataset branch) with gaussian_radius / draw_umich_gaussian of det3d/core/utils/center_utils.py:17-64, for a whole batch
  * [B, T] and every target set in two launches.  Purely additive: fd_abi_version() stays 8.
