@@ -1,5 +1,6 @@
-"""Mixed-precision training of the dense stride-1 convolutions (the RPN neck) on the bf16 NHWC kernels: the autograd surface
-(conv2d_bf16), the predicate that says where it applies (conv_takes_bf16), and the walk over a ZeroPad2d / Conv2d / BatchNorm2d / ReLU
+"""Mixed-precision training of the dense stride-1 convolutions (the RPN neck, the CenterHead) on the bf16 NHWC kernels: the autograd
+surfaces (conv2d_bf16; head_tail_bf16 for the head's final convolutions), the predicates that say where they apply (conv_takes_bf16 for
+the neck, head_conv_takes_bf16 / head_tail_takes_bf16 for the head), and the walk over a ZeroPad2d / Conv2d / BatchNorm2d / ReLU
 stack that RPN.train_dtype = torch.bfloat16 switches on (run_stack_bf16).  The recipe is the sparse backbone's: bf16 activations, fp32
 master weights packed to bf16 on the device every step, fp32 accumulation, fp32 weight gradients and BatchNorm statistics."""
 import torch
@@ -10,17 +11,19 @@ from .sparse import relu_to_bf16
 
 
 class _Conv2dBf16Function(torch.autograd.Function):
-    """One stride-1 convolution (3 x 3 / padding 1 or 1 x 1 / padding 0, no bias) on x [B, H, W, Cin] bf16 with the fp32 OIHW weight.
+    """One stride-1 convolution (3 x 3 / padding 1 or 1 x 1 / padding 0) on x [B, H, W, Cin] bf16 with the fp32 OIHW weight and, where the
+    layer has one, its fp32 bias.
 
-    forward:  fd_conv2d_pack_weight_dev (mode 0) + fd_conv2d_nhwc_bf16 (no bias, no ReLU);
+    forward:  fd_conv2d_pack_weight_dev (mode 0) + fd_conv2d_nhwc_bf16 (its bias argument, no ReLU);
     backward: dX on fd_conv2d_nhwc_bf16 again, a Cout -> Cin convolution of dY with the flipped, transposed weights
-              (fd_conv2d_pack_weight_dev mode 1); dW on fd_conv2d_wgrad_bf16, fp32.  Saves the inputs only.
+              (fd_conv2d_pack_weight_dev mode 1); dW on fd_conv2d_wgrad_bf16, fp32; dbias = the column sums of the bf16 dY
+              (fd_rows_colsum).  Saves the inputs only.
     Nothing here reads a value back to the host."""
 
     @staticmethod
-    def forward(ctx, x, weight, ks):
+    def forward(ctx, x, weight, ks, bias=None):
         wpk = hip_ops.pack_conv2d_weight_device(weight)
-        y = hip_ops.conv2d_nhwc_bf16(x, wpk, None, weight.shape[0], ks, stride=1, relu=False)
+        y = hip_ops.conv2d_nhwc_bf16(x, wpk, bias, weight.shape[0], ks, stride=1, relu=False)
         ctx.save_for_backward(x, weight)
         ctx.ks = ks
         return y
@@ -36,13 +39,26 @@ class _Conv2dBf16Function(torch.autograd.Function):
             dx = hip_ops.conv2d_nhwc_bf16(dy, wpk, None, weight.shape[1], ctx.ks, stride=1, relu=False)
         if ctx.needs_input_grad[1]:
             dw = hip_ops.conv2d_wgrad_bf16(x, dy, ctx.ks)
-        return dx, dw, None
+        if len(ctx.needs_input_grad) == 3:  # the call without a bias
+            return dx, dw, None
+        db = _colsum(dy.view(-1, dy.shape[3])) if ctx.needs_input_grad[3] else None
+        return dx, dw, None, db
 
 
-def conv2d_bf16(x_nhwc, weight, ks):
+def _colsum(rows):
+    """fp32 column sums of the bf16 [n, C] rows, C % 32 == 0, on fd_rows_colsum; it takes up to 128 columns, so a wider matrix (the 64 G
+    channels of a SepHead's batched branch convolution) goes block of columns by block of columns"""
+    c = rows.shape[1]
+    if c <= 128 and c & (c - 1) == 0:
+        return hip_ops.rows_colsum(rows)
+    blk = 128 if c % 128 == 0 else 64 if c % 64 == 0 else 32
+    return torch.cat([hip_ops.rows_colsum(rows[:, j:j + blk].contiguous()) for j in range(0, c, blk)])
+
+
+def conv2d_bf16(x_nhwc, weight, ks, bias=None):
     """y [B, H, W, Cout] bf16 = the stride-1 convolution of x [B, H, W, Cin] (bf16, contiguous, on the device) with ``weight``, the module's
-    fp32 [Cout, Cin, ks, ks] parameter; ks 3 pads by 1, ks 1 by 0.  Differentiable in both.  Raises where the kernels do not apply: there
-    is no fallback here."""
+    fp32 [Cout, Cin, ks, ks] parameter, plus ``bias`` (fp32 [Cout], added in fp32 before the one rounding) where given; ks 3 pads by 1,
+    ks 1 by 0.  Differentiable in x, weight and bias.  Raises where the kernels do not apply: there is no fallback here."""
     if not (isinstance(x_nhwc, torch.Tensor) and x_nhwc.is_cuda and x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4
             and x_nhwc.is_contiguous()):
         raise hip_ops.FutureDetHipError("conv2d_bf16: x must be a contiguous bf16 [B, H, W, Cin] tensor on the HIP device")
@@ -50,7 +66,176 @@ def conv2d_bf16(x_nhwc, weight, ks):
             and tuple(weight.shape[1:]) == (x_nhwc.shape[3], ks, ks) and weight.shape[0] % 32 == 0 and weight.shape[1] % 32 == 0):
         raise hip_ops.FutureDetHipError("conv2d_bf16: needs an fp32 [Cout, Cin, %s, %s] weight on x's device with Cin = %d and both channel "
                                         "counts multiples of 32 (got %s %s)" % (ks, ks, x_nhwc.shape[3], tuple(weight.shape), weight.dtype))
-    return _Conv2dBf16Function.apply(x_nhwc, weight.contiguous(), ks)
+    if bias is None:
+        return _Conv2dBf16Function.apply(x_nhwc, weight.contiguous(), ks)
+    if not (bias.dtype == torch.float32 and bias.device == x_nhwc.device and tuple(bias.shape) == (weight.shape[0],)):
+        raise hip_ops.FutureDetHipError("conv2d_bf16: needs an fp32 [%d] bias on x's device (got %s %s)"
+                                        % (weight.shape[0], tuple(bias.shape), bias.dtype))
+    return _Conv2dBf16Function.apply(x_nhwc, weight.contiguous(), ks, bias.contiguous())
+
+
+class _HeadTailBf16Function(torch.autograd.Function):
+    """The final convolutions of one SepHead's branches (3 x 3 / padding 1, Cin % 32 == 0, at most 16 output channels, a bias) in one
+    launch per pass on fd_head_tail_bf16.hip: bf16 NHWC in, fp32 NCHW out.  ``meta`` holds, per group, (index of its x among the distinct
+    x tensors, first channel); the tensors are the distinct xs, then every group's weight, then every group's bias.  Saves the inputs
+    only; the input gradient of an x is one bf16 tensor that every group fills its own channel slice of."""
+
+    @staticmethod
+    def forward(ctx, meta, n_x, *tensors):
+        n = len(meta)
+        xs, ws, bs = tensors[:n_x], tensors[n_x:n_x + n], tensors[n_x + n:]
+        ys = hip_ops.head_tail_forward([(xs[xi], c0, ws[i], bs[i]) for i, (xi, c0) in enumerate(meta)])
+        ctx.save_for_backward(*tensors)
+        ctx.meta, ctx.n_x = meta, n_x
+        return tuple(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dys):
+        meta, n_x, n = ctx.meta, ctx.n_x, len(ctx.meta)
+        tensors = ctx.saved_tensors
+        xs, ws = tensors[:n_x], tensors[n_x:n_x + n]
+        dys = [dy.to(torch.float32).contiguous() for dy in dys]
+        need = ctx.needs_input_grad[2:]
+        dxs = [None] * n_x
+        for j in range(n_x):
+            if need[j]:
+                covered = sum(ws[i].shape[1] for i, (xi, _) in enumerate(meta) if xi == j)
+                dxs[j] = (torch.empty_like if covered == xs[j].shape[3] else torch.zeros_like)(xs[j])
+        todo = [(dxs[xi], c0, ws[i], dys[i]) for i, (xi, c0) in enumerate(meta) if dxs[xi] is not None]
+        if todo:
+            hip_ops.head_tail_dgrad(todo)
+        dws, dbs = [None] * n, [None] * n
+        idx = [i for i in range(n) if need[n_x + i] or need[n_x + n + i]]
+        if idx:
+            got = hip_ops.head_tail_wgrad([(xs[meta[i][0]], meta[i][1], ws[i].shape[1], dys[i]) for i in idx])
+            for i, (dw, db) in zip(idx, got):
+                dws[i], dbs[i] = (dw if need[n_x + i] else None), (db if need[n_x + n + i] else None)
+        return (None, None) + tuple(dxs) + tuple(dws) + tuple(dbs)
+
+
+def head_tail_bf16(groups):
+    """The final convolutions of a SepHead in one call: ``groups`` is a list of (x, weight, bias) or (x, weight, bias, c0); x a contiguous
+    bf16 [B, H, W, C] device tensor of which the group reads channels c0 .. c0 + Cin - 1 (c0 = 0 by default, a multiple of 8; several
+    groups may read slices of one x, which must then not overlap), weight fp32 [k, Cin, 3, 3] with Cin % 32 == 0 and 1 <= k <= 16, bias
+    fp32 [k].  Returns the list of fp32 NCHW [B, k, H, W] maps: weights rounded to bf16, fp32 accumulation, fp32 bias, no second
+    rounding.  Differentiable in every x, weight and bias.  Raises where the kernels do not apply."""
+    xs, meta, ws, bs = [], [], [], []
+    for g in groups:
+        x, w, b = g[0], g[1], g[2]
+        c0 = int(g[3]) if len(g) > 3 else 0
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()):
+            raise hip_ops.FutureDetHipError("head_tail_bf16: x must be a contiguous bf16 [B, H, W, C] tensor on the HIP device")
+        if not (w.dtype == torch.float32 and w.device == x.device and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and w.shape[1] % 32 == 0
+                and 1 <= w.shape[0] <= 16 and b is not None and b.dtype == torch.float32 and b.device == x.device
+                and tuple(b.shape) == (w.shape[0],)):
+            raise hip_ops.FutureDetHipError("head_tail_bf16: needs an fp32 [k, Cin, 3, 3] weight with Cin %% 32 == 0 and 1 <= k <= 16 and an "
+                                            "fp32 [k] bias on x's device (got %s)" % (tuple(w.shape),))
+        for j, other in enumerate(xs):
+            if other is x:
+                break
+        else:
+            j = len(xs)
+            xs.append(x)
+        meta.append((j, c0))
+        ws.append(w.contiguous())
+        bs.append(b.contiguous())
+    return list(_HeadTailBf16Function.apply(tuple(meta), len(xs), *(xs + ws + bs)))
+
+
+def _conv3_takes(conv, x):
+    """an nn.Conv2d with a 3 x 3 kernel, padding 1, stride 1, dilation 1, groups 1, an fp32 weight on x's device, in_channels % 32 == 0"""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and tuple(conv.padding) == (1, 1) and conv.padding_mode == "zeros"
+            and conv.stride == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 32 == 0
+            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device)
+
+
+def head_conv_takes_bf16(conv, x):
+    """True where conv2d_bf16 (with the layer's bias, if it has one) can take the place of ``conv`` in the head: a 3 x 3 / padding 1 /
+    stride 1 nn.Conv2d, dilation 1, groups 1, in_channels and out_channels multiples of 32, an fp32 weight on x's device."""
+    return _conv3_takes(conv, x) and conv.out_channels % 32 == 0
+
+
+def head_tail_takes_bf16(conv, x):
+    """True where ``conv`` can be a group of head_tail_bf16: a 3 x 3 / padding 1 / stride 1 nn.Conv2d with a bias, dilation 1, groups 1,
+    in_channels a multiple of 32, at most 16 output channels, an fp32 weight on x's device."""
+    return _conv3_takes(conv, x) and conv.bias is not None and 1 <= conv.out_channels <= 16
+
+
+def _to_nhwc(x):
+    """contiguous [B, H, W, C] memory of an NCHW-shaped map (no copy for a channels-last one)"""
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+def run_head_stack_bf16(mods, x):
+    """The modules ``mods`` (a list of Conv2d / BatchNorm2d / ReLU of the CenterHead) on ``x`` in mixed precision.  ``x`` is NCHW-shaped:
+    a bf16 channels-last device map, or the fp32 form of one in front of a BatchNorm2d; the result is bf16 channels-last.
+
+      * a convolution that satisfies head_conv_takes_bf16: conv2d_bf16 with its bias;
+      * any other convolution (bev_conv's 6- and 16-channel layers): the module on an fp32 copy of its input, rounded to bf16;
+      * BatchNorm2d: bn(x.float()) with fp32 batch and running statistics, the ReLU that follows, one rounding to bf16."""
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        if isinstance(m, nn.Conv2d):
+            if head_conv_takes_bf16(m, x):
+                x = conv2d_bf16(_to_nhwc(x.to(torch.bfloat16)), m.weight, 3, m.bias).permute(0, 3, 1, 2)
+            else:
+                x = m(x.float()).to(torch.bfloat16)
+            i += 1
+        elif isinstance(m, nn.BatchNorm2d):
+            out = m(x.float())
+            if isinstance(nxt, nn.ReLU):
+                x = relu_to_bf16(out)
+                i += 2
+            else:
+                x = out.to(torch.bfloat16)
+                i += 1
+        elif isinstance(m, nn.ReLU):  # out of place: the input may be saved for a backward
+            x = torch.relu(x).to(torch.bfloat16)
+            i += 1
+        else:
+            raise NotImplementedError("run_head_stack_bf16: no mixed-precision form of %s" % type(m).__name__)
+    return x
+
+
+def sep_head_bf16(task, x):
+    """SepHead.forward_modules in mixed precision on the bf16 channels-last device map ``x`` (NCHW-shaped): the dict of the module chain,
+    ``feats`` bf16 channels-last, every branch's map fp32 NCHW contiguous.
+
+      * forecast_conv: run_head_stack_bf16;
+      * the leading convolutions of the branches, where every branch has one that satisfies head_conv_takes_bf16 and they agree in shape:
+        ONE conv2d_bf16 call on torch.cat of their weights and biases (autograd splits the gradients back); otherwise each on its own;
+      * each branch's own BatchNorm2d + ReLU on its channels of that result;
+      * the final convolutions that satisfy head_tail_takes_bf16: ONE head_tail_bf16 call; any other runs its module on an fp32 copy."""
+    ret = {}
+    if task.forecast_feature:
+        x = run_head_stack_bf16(list(task.forecast_conv.children()), x)
+        ret["feats"] = x
+    names = list(task.heads)
+    stacks = [list(getattr(task, h).children()) for h in names]
+    first = [s[0] for s in stacks]
+    if (len(names) > 1 and all(len(s) >= 2 and head_conv_takes_bf16(s[0], x) and s[0].bias is not None for s in stacks)
+            and len(set((c.in_channels, c.out_channels) for c in first)) == 1):
+        y = conv2d_bf16(_to_nhwc(x), torch.cat([c.weight for c in first]), 3, torch.cat([c.bias for c in first])).permute(0, 3, 1, 2)
+        parts = y.float().split(first[0].out_channels, dim=1)  # one conversion and one split: their backward is one cat
+        feats = [run_head_stack_bf16(s[1:-1], p) for s, p in zip(stacks, parts)]
+    else:
+        feats = [run_head_stack_bf16(s[:-1], x) for s in stacks]
+    groups, tails = [], []
+    for h, s, f in zip(names, stacks, feats):
+        f = f.to(torch.bfloat16)
+        if head_tail_takes_bf16(s[-1], f):
+            groups.append((_to_nhwc(f), s[-1].weight, s[-1].bias))
+            tails.append(h)
+            ret[h] = None  # keeps the chain's key order
+        else:
+            ret[h] = s[-1](f.float()).contiguous()
+    if groups:
+        for h, y in zip(tails, head_tail_bf16(groups)):
+            ret[h] = y
+    return ret
 
 
 def _conv_takes(conv, x, padding):

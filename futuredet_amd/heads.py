@@ -321,6 +321,7 @@ class CenterHead(nn.Module):
         self.compute_dtype = torch.float32
         self.fused_loss = False  # True: loss() of a standard / dense head runs on fd_loss.hip for fp32 maps on the device
         self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the head runs on fd_dense_bn.hip (handed to the tasks)
+        self.train_dtype = torch.float32  # training: torch.bfloat16 = mixed precision on the bf16 NHWC convolutions (forward_mixed)
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
         self.logger.info("Finish CenterHead Initialization")
@@ -346,7 +347,38 @@ class CenterHead(nn.Module):
             ret_dicts.append(task(xin, True) if fused else task(xin))
         return ret_dicts
 
+    def forward_mixed(self, x, bev_map=None):
+        """Training-mode forward in mixed precision (train_dtype = torch.bfloat16, device maps, gradients enabled): the fp32 NCHW input
+        is converted once to bf16 channels-last; shared_conv, forecast_conv and the leading convolution of every branch run on
+        dense_train.conv2d_bf16 with their bias (the leading convolutions of one SepHead as ONE convolution on the concatenated weights),
+        BatchNorm2d stays each module's own with fp32 statistics (bn(x.float()), ReLU, one rounding), and the final convolutions of a
+        SepHead are one dense_train.head_tail_bf16 call (fd_head_tail_bf16.hip) whose maps are fp32 NCHW.  ``feats`` and the
+        forecast-feature concat stay bf16 in here; every returned map is fp32 and NCHW-contiguous, what loss() and the fused loss read.
+        Layers the kernels do not take (bev_conv's 6- and 16-channel convolutions, more than 16 final channels) run their module on an
+        fp32 copy.  ``fused_bn`` has no effect here, as in RPN.forward_mixed."""
+        from .dense_train import run_head_stack_bf16, sep_head_bf16
+
+        x = run_head_stack_bf16(list(self.shared_conv.children()), x.to(torch.bfloat16, memory_format=torch.channels_last))
+        if self.bev_map:
+            x = x + run_head_stack_bf16(list(self.bev_conv.children()), bev_map.to(torch.bfloat16, memory_format=torch.channels_last))
+        ret_dicts = []
+        for i, task in enumerate(self.tasks):
+            xin = torch.cat([x, ret_dicts[i - 1]["feats"]], dim=1) if i != 0 and self.forecast_feature else x
+            ret_dicts.append(sep_head_bf16(task, xin))
+        if self.forecast_feature:
+            ret_dicts = [dict((k, v.to(torch.float32, memory_format=torch.contiguous_format) if k == "feats" else v) for k, v in d.items())
+                         for d in ret_dicts]
+        return ret_dicts
+
     def forward(self, x, bev_map=None, *kwargs):
+        if self.training:
+            if self.train_dtype not in (torch.float32, torch.bfloat16):
+                raise ValueError("CenterHead: train_dtype must be torch.float32 or torch.bfloat16 (got %s)" % (self.train_dtype,))
+            if self.train_dtype == torch.bfloat16 and self.dcn_head:
+                raise NotImplementedError("CenterHead(dcn_head=True): train_dtype = torch.bfloat16 is not supported, the deformable head "
+                                          "trains in fp32 only")
+            if self.train_dtype == torch.bfloat16 and x.is_cuda and torch.is_grad_enabled():
+                return self.forward_mixed(x, bev_map)
         if self.training or not x.is_cuda:
             return self.forward_modules(x, bev_map)
         if self.compute_dtype not in (torch.bfloat16, torch.float32):

@@ -586,6 +586,103 @@ def conv2d_wgrad_bf16(x_nhwc, dy_nhwc, ks):
     return dw
 
 
+# ------------------------------------------------------------------------------------------------ head tail (bf16 training)
+def head_tail_max_groups():
+    """Group records one launch of the head-tail kernels takes; the wrappers below split longer lists."""
+    return int(_lib.load().fd_head_tail_bf16_max_groups())
+
+
+def head_tail_wgrad_chunk():
+    """Input pixels per partial of head_tail_wgrad: a constant of the library, part of its summation order."""
+    return int(_lib.load().fd_head_tail_wgrad_bf16_chunk())
+
+
+def _head_tail_group(what, x, c0, w, bias, y):
+    """One fd_head_tail_group: channels c0 .. c0 + cin - 1 of the contiguous bf16 [B, H, W, C] tensor ``x``, the fp32 [k, cin, 3, 3] ``w``,
+    the fp32 [k] ``bias`` (None where the entry point does not look at it) and the fp32 [B, k, H, W] ``y``."""
+    x = _dev(x, what + ": x", torch.bfloat16)
+    w = _dev(w, what + ": weight", torch.float32)
+    y = _dev(y, what + ": y", torch.float32)
+    if bias is not None:
+        bias = _dev(bias, what + ": bias", torch.float32)
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or y.dim() != 4:
+        raise FutureDetHipError("%s: needs x [B, H, W, C], a [k, cin, 3, 3] weight and y [B, k, H, W] (got %s, %s, %s)"
+                                % (what, tuple(x.shape), tuple(w.shape), tuple(y.shape)))
+    k, cin = int(w.shape[0]), int(w.shape[1])
+    B, H, W, C = x.shape
+    if tuple(y.shape) != (B, k, H, W) or (bias is not None and tuple(bias.shape) != (k,)):
+        raise FutureDetHipError("%s: y must be [%d, %d, %d, %d] and the bias [%d] (got %s, %s)"
+                                % (what, B, k, H, W, k, tuple(y.shape), None if bias is None else tuple(bias.shape)))
+    if c0 < 0 or c0 % 8 or c0 + cin > C:
+        raise FutureDetHipError("%s: channels %d .. %d are no 16-byte aligned slice of the %d channels of x" % (what, c0, c0 + cin - 1, C))
+    rec = _lib.HeadTailGroup(x.data_ptr() + 2 * c0, w.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), C, cin, k)
+    return rec, (B, H, W)
+
+
+def _head_tail_launch(what, entry, records, with_workspace=False):
+    """``entry`` over the records (rec, (B, H, W)), at most head_tail_max_groups() per launch"""
+    L = _lib.load()
+    shapes = set(s for _, s in records)
+    if len(shapes) != 1:
+        raise FutureDetHipError("%s: needs at least one group, all over the same B x H x W pixels (got %s)" % (what, sorted(shapes)))
+    B, H, W = shapes.pop()
+    step = head_tail_max_groups()
+    for i in range(0, len(records), step):
+        part = [r for r, _ in records[i:i + step]]
+        arr = (_lib.HeadTailGroup * len(part))(*part)
+        if with_workspace:
+            nbytes = L.fd_head_tail_wgrad_bf16_workspace_bytes(B, H, W, sum(r.cin for r in part))
+            if nbytes == 0:
+                raise FutureDetHipError("%s: unsupported problem %d x %d x %d, cin %s" % (what, B, H, W, [r.cin for r in part]))
+            ws = workspace.get("head_tail_wgrad", nbytes, torch.device("cuda", torch.cuda.current_device()))
+            check(getattr(L, entry)(arr, len(part), B, H, W, _p(ws), ws.numel(), _stream()), entry)
+        else:
+            check(getattr(L, entry)(arr, len(part), B, H, W, _stream()), entry)
+
+
+def head_tail_forward(groups):
+    """fd_head_tail_forward_bf16: for every group (x, c0, weight, bias) the 3 x 3 / padding 1 convolution of channels c0 .. c0 + cin - 1 of
+    the contiguous bf16 [B, H, W, C] tensor x with the fp32 [k, cin, 3, 3] weight (k <= 16, rounded to bf16 inside) plus the fp32 bias ->
+    a list of fp32 NCHW [B, k, H, W] maps.  One launch per head_tail_max_groups() groups."""
+    recs, ys = [], []
+    for x, c0, w, bias in groups:
+        x = _dev(x, "head_tail_forward: x", torch.bfloat16)
+        w = _dev(w, "head_tail_forward: weight", torch.float32)
+        if x.dim() != 4 or w.dim() != 4:
+            raise FutureDetHipError("head_tail_forward: needs x [B, H, W, C] and a [k, cin, 3, 3] weight (got %s, %s)" % (tuple(x.shape), tuple(w.shape)))
+        if bias is None:
+            raise FutureDetHipError("head_tail_forward: every group needs a bias")
+        y = torch.empty((x.shape[0], w.shape[0], x.shape[1], x.shape[2]), dtype=torch.float32, device=x.device)
+        recs.append(_head_tail_group("head_tail_forward", x, c0, w, bias, y))
+        ys.append(y)
+    _head_tail_launch("head_tail_forward", "fd_head_tail_forward_bf16", recs)
+    return ys
+
+
+def head_tail_dgrad(groups):
+    """fd_head_tail_dgrad_bf16: for every group (dx, c0, weight, dy) writes the input gradient of head_tail_forward's convolution, bf16,
+    into channels c0 .. c0 + cin - 1 of the contiguous bf16 [B, H, W, C] tensor dx (the other channels are not touched); dy fp32
+    [B, k, H, W]."""
+    recs = [_head_tail_group("head_tail_dgrad", dx, c0, w, None, dy) for dx, c0, w, dy in groups]
+    _head_tail_launch("head_tail_dgrad", "fd_head_tail_dgrad_bf16", recs)
+
+
+def head_tail_wgrad(groups):
+    """fd_head_tail_wgrad_bf16: for every group (x, c0, cin, dy) -> (dW fp32 [k, cin, 3, 3], dbias fp32 [k]) of head_tail_forward's
+    convolution; deterministic, no atomics.  dbias sums the unrounded dy."""
+    recs, out = [], []
+    for x, c0, cin, dy in groups:
+        dy = _dev(dy, "head_tail_wgrad: dy", torch.float32)
+        if dy.dim() != 4:
+            raise FutureDetHipError("head_tail_wgrad: dy must be [B, k, H, W] (got %s)" % (tuple(dy.shape),))
+        dw = torch.empty((dy.shape[1], cin, 3, 3), dtype=torch.float32, device=dy.device)
+        db = torch.empty((dy.shape[1],), dtype=torch.float32, device=dy.device)
+        recs.append(_head_tail_group("head_tail_wgrad", x, c0, dw, db, dy))
+        out.append((dw, db))
+    _head_tail_launch("head_tail_wgrad", "fd_head_tail_wgrad_bf16", recs, with_workspace=True)
+    return out
+
+
 def pack_conv2d_weight_f32(w_oihw):
     """[Cout, Cin, k, k] float32 -> MFMA-fragment-ordered fp32 weights on the same device (fd_conv2d_f32_pack_weight)."""
     L = _lib.load()

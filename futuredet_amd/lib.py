@@ -67,6 +67,10 @@ class LossTask(ctypes.Structure):  # struct fd_loss_task
                 ("anno_box", c_void_p * 7), ("C", ctypes.c_int32), ("sig", c_void_p), ("d_hm", c_void_p), ("d_maps", c_void_p * 7)]
 
 
+class HeadTailGroup(ctypes.Structure):  # struct fd_head_tail_group
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("x_stride", c_i64), ("cin", c_int), ("k", c_int)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -166,6 +170,12 @@ SIGNATURES = {
     "fd_conv2d_wgrad_bf16_chunk": (c_int, []),
     "fd_conv2d_wgrad_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fd_conv2d_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fd_head_tail_bf16_max_groups": (c_int, []),
+    "fd_head_tail_wgrad_bf16_chunk": (c_int, []),
+    "fd_head_tail_wgrad_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fd_head_tail_forward_bf16": (c_int, [ctypes.POINTER(HeadTailGroup), c_int, c_int, c_int, c_int, c_void_p]),
+    "fd_head_tail_dgrad_bf16": (c_int, [ctypes.POINTER(HeadTailGroup), c_int, c_int, c_int, c_int, c_void_p]),
+    "fd_head_tail_wgrad_bf16": (c_int, [ctypes.POINTER(HeadTailGroup), c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "fd_dense_gather": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p]),
     "fd_pillar_train_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "fd_pillar_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_float, c_float, c_float,

@@ -552,6 +552,44 @@ int fd_conv2d_wgrad_bf16(const void *x, const void *dy, int B, int H, int W, int
                          size_t workspace_bytes, float *dw, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Mixed-precision training of the CenterHead's final convolutions (fd_head_tail_bf16.hip): 3 x 3, padding 1, stride 1, cin % 32 == 0
+ * input channels, 1 <= k <= 16 output channels, a bias; bf16 NHWC input, fp32 NCHW output for the loss.  Purely additive:
+ * fd_abi_version() stays 8.  One launch serves up to fd_head_tail_bf16_max_groups() group records (a longer array is FD_EINVAL: the
+ * caller splits it); all groups cover the same B x H x W pixels.  A record (fd_head_tail_group): x, bf16, channel c of pixel p at
+ * x[p * x_stride + c] with x_stride >= cin, x_stride % 8 == 0 and x 16-byte aligned -- so a group can read, and its input gradient fill,
+ * a cin-channel slice of a wider NHWC tensor; w [k][cin][3][3] fp32; bias [k] fp32; y [B][k][H][W] fp32.  What each entry point does
+ * with them:
+ *   fd_head_tail_forward_bf16: reads x, w (rounded to bf16 inside, nearest even) and bias; writes y = fp32 accumulation on the matrix
+ *                     core + bias, not rounded again.
+ *   fd_head_tail_dgrad_bf16: reads w and y (= dy, rounded to bf16 as the operand); WRITES x (= dx: fp32 accumulation rounded once to
+ *                     bf16, channels 0 .. cin - 1 of every pixel and nothing else); bias is not looked at and may be null.
+ *   fd_head_tail_wgrad_bf16: reads x and y (= dy); WRITES w (= dW fp32, dy rounded to bf16 as the operand) and bias (= dbias fp32, the
+ *                     sum of the unrounded dy in a fixed order).
+ *   fd_head_tail_wgrad_bf16: the input pixels, in (b, y, x) order, are cut into chunks of fd_head_tail_wgrad_bf16_chunk() (a constant of
+ *                     the library); one fp32 [10][cin][16] partial per (group, chunk) -- nine taps and the bias gradient -- goes to `workspace`
+ *                     (fd_head_tail_wgrad_bf16_workspace_bytes with cin_sum = the sum of the groups' cin; 0 = bad arguments) and the
+ *                     partials are summed in chunk order: bit-identical from run to run, no atomics.  The workspace need not be
+ *                     initialised: every word that is read has been written by the same call.
+ * Every entry point validates before any device work (FD_EINVAL + fd_last_error), neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct fd_head_tail_group {
+    void *x;
+    float *w;
+    float *bias;
+    void *y;
+    int64_t x_stride;
+    int cin;
+    int k;
+} fd_head_tail_group;
+int fd_head_tail_bf16_max_groups(void);
+int fd_head_tail_wgrad_bf16_chunk(void);
+size_t fd_head_tail_wgrad_bf16_workspace_bytes(int B, int H, int W, int cin_sum);
+int fd_head_tail_forward_bf16(const fd_head_tail_group *groups, int n_groups, int B, int H, int W, fd_stream_t stream);
+int fd_head_tail_dgrad_bf16(const fd_head_tail_group *groups, int n_groups, int B, int H, int W, fd_stream_t stream);
+int fd_head_tail_wgrad_bf16(const fd_head_tail_group *groups, int n_groups, int B, int H, int W, void *workspace, size_t workspace_bytes,
+                            fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training targets: AssignLabel's heat maps and box rows (fd_targets.hip) -- det3d/datasets/pipelines/preprocess.py:336-910
  * (NuScenesDataset branch) with gaussian_radius / draw_umich_gaussian of det3d/core/utils/center_utils.py:17-64, for a whole batch
  * [B, T] and every target set in two launches.  Purely additive: fd_abi_version() stays 8.
