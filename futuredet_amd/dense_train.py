@@ -2,11 +2,13 @@
 surfaces (conv2d_bf16; head_tail_bf16 for the head's final convolutions), the predicates that say where they apply (conv_takes_bf16 for
 the neck, head_conv_takes_bf16 / head_tail_takes_bf16 for the head), and the walk over a ZeroPad2d / Conv2d / BatchNorm2d / ReLU
 stack that RPN.train_dtype = torch.bfloat16 switches on (run_stack_bf16).  The recipe is the sparse backbone's: bf16 activations, fp32
-master weights packed to bf16 on the device every step, fp32 accumulation, fp32 weight gradients and BatchNorm statistics."""
+master weights packed to bf16 on the device every step, fp32 accumulation, fp32 weight gradients and BatchNorm statistics.  With
+``fused_bn`` the walks hand every BatchNorm2d (+ ReLU) that dense_bn.batch_norm2d_nhwc_fusable accepts to
+dense_bn.batch_norm2d_act_nhwc (fd_dense_bn_nhwc.hip: bf16 channels-last in and out, no fp32 copy of the map)."""
 import torch
 from torch import nn
 
-from . import hip_ops
+from . import dense_bn, hip_ops
 from .sparse import relu_to_bf16
 
 
@@ -167,13 +169,30 @@ def _to_nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
-def run_head_stack_bf16(mods, x):
+def _batch_norm_bf16(m, nxt, x, fused_bn):
+    """BatchNorm2d ``m`` (+ the nn.ReLU ``nxt`` behind it) on the NCHW-shaped map ``x`` -> (bf16 result, modules consumed).  With
+    ``fused_bn`` and a fusable module: one batch_norm2d_act_nhwc call.  Otherwise the un-fused recipe: bn(x.float()) with fp32 batch and
+    running statistics, the ReLU, one rounding to bf16."""
+    act = isinstance(nxt, nn.ReLU)
+    if fused_bn and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4:
+        # torch's own convolutions (stride 2, transposed) may hand back NCHW memory: the permuting copy that the next conv2d_bf16 would
+        # make moves in front of the BatchNorm2d (no copy for a channels-last map)
+        xc = x.contiguous(memory_format=torch.channels_last)
+        if dense_bn.batch_norm2d_nhwc_fusable(xc, m):
+            return dense_bn.batch_norm2d_act_nhwc(xc, m, relu=act), 1 + act
+    out = m(x.float())
+    return (relu_to_bf16(out) if act else out.to(torch.bfloat16)), 1 + act
+
+
+def run_head_stack_bf16(mods, x, fused_bn=False):
     """The modules ``mods`` (a list of Conv2d / BatchNorm2d / ReLU of the CenterHead) on ``x`` in mixed precision.  ``x`` is NCHW-shaped:
     a bf16 channels-last device map, or the fp32 form of one in front of a BatchNorm2d; the result is bf16 channels-last.
 
       * a convolution that satisfies head_conv_takes_bf16: conv2d_bf16 with its bias;
       * any other convolution (bev_conv's 6- and 16-channel layers): the module on an fp32 copy of its input, rounded to bf16;
-      * BatchNorm2d: bn(x.float()) with fp32 batch and running statistics, the ReLU that follows, one rounding to bf16."""
+      * BatchNorm2d: bn(x.float()) with fp32 batch and running statistics, the ReLU that follows, one rounding to bf16; with
+        ``fused_bn``, a module that dense_bn.batch_norm2d_nhwc_fusable accepts on the bf16 channels-last map is one
+        batch_norm2d_act_nhwc call instead (relu=False where no ReLU follows)."""
     i = 0
     while i < len(mods):
         m = mods[i]
@@ -185,13 +204,8 @@ def run_head_stack_bf16(mods, x):
                 x = m(x.float()).to(torch.bfloat16)
             i += 1
         elif isinstance(m, nn.BatchNorm2d):
-            out = m(x.float())
-            if isinstance(nxt, nn.ReLU):
-                x = relu_to_bf16(out)
-                i += 2
-            else:
-                x = out.to(torch.bfloat16)
-                i += 1
+            x, used = _batch_norm_bf16(m, nxt, x, fused_bn)
+            i += used
         elif isinstance(m, nn.ReLU):  # out of place: the input may be saved for a backward
             x = torch.relu(x).to(torch.bfloat16)
             i += 1
@@ -200,7 +214,7 @@ def run_head_stack_bf16(mods, x):
     return x
 
 
-def sep_head_bf16(task, x):
+def sep_head_bf16(task, x, fused_bn=False):
     """SepHead.forward_modules in mixed precision on the bf16 channels-last device map ``x`` (NCHW-shaped): the dict of the module chain,
     ``feats`` bf16 channels-last, every branch's map fp32 NCHW contiguous.
 
@@ -208,26 +222,43 @@ def sep_head_bf16(task, x):
       * the leading convolutions of the branches, where every branch has one that satisfies head_conv_takes_bf16 and they agree in shape:
         ONE conv2d_bf16 call on torch.cat of their weights and biases (autograd splits the gradients back); otherwise each on its own;
       * each branch's own BatchNorm2d + ReLU on its channels of that result;
-      * the final convolutions that satisfy head_tail_takes_bf16: ONE head_tail_bf16 call; any other runs its module on an fp32 copy."""
+      * the final convolutions that satisfy head_tail_takes_bf16: ONE head_tail_bf16 call; any other runs its module on an fp32 copy.
+
+    With ``fused_bn``, where the batched convolution ran, there are at most 8 branches and every branch's middle is exactly a fusable
+    BatchNorm2d + ReLU: ONE grouped batch_norm2d_act_nhwc call on the whole map (module j on branch j's channels), no fp32 copy and no
+    split, and the final convolutions read their channel slices of that one tensor through head_tail_bf16's c0.  Where the branches
+    run on their own, each BatchNorm2d is fused where it can be (run_head_stack_bf16); behind a batched convolution whose branches do
+    not qualify together, the un-fused recipe stays."""
     ret = {}
     if task.forecast_feature:
-        x = run_head_stack_bf16(list(task.forecast_conv.children()), x)
+        x = run_head_stack_bf16(list(task.forecast_conv.children()), x, fused_bn)
         ret["feats"] = x
     names = list(task.heads)
     stacks = [list(getattr(task, h).children()) for h in names]
     first = [s[0] for s in stacks]
+    whole = None  # the grouped path: every branch's input of its final convolution is a channel slice of this one map
     if (len(names) > 1 and all(len(s) >= 2 and head_conv_takes_bf16(s[0], x) and s[0].bias is not None for s in stacks)
             and len(set((c.in_channels, c.out_channels) for c in first)) == 1):
         y = conv2d_bf16(_to_nhwc(x), torch.cat([c.weight for c in first]), 3, torch.cat([c.bias for c in first])).permute(0, 3, 1, 2)
-        parts = y.float().split(first[0].out_channels, dim=1)  # one conversion and one split: their backward is one cat
-        feats = [run_head_stack_bf16(s[1:-1], p) for s, p in zip(stacks, parts)]
+        width = first[0].out_channels
+        if (fused_bn and all(len(s) == 4 and isinstance(s[2], nn.ReLU) for s in stacks)
+                and dense_bn.batch_norm2d_nhwc_group_fusable(y, [s[1] for s in stacks])):
+            whole = dense_bn.batch_norm2d_act_nhwc(y, [s[1] for s in stacks], relu=True)
+            whole_nhwc = _to_nhwc(whole)
+            feats = [whole[:, j * width:(j + 1) * width] for j in range(len(names))]
+        else:
+            parts = y.float().split(width, dim=1)  # one conversion and one split: their backward is one cat
+            feats = [run_head_stack_bf16(s[1:-1], p) for s, p in zip(stacks, parts)]
     else:
-        feats = [run_head_stack_bf16(s[:-1], x) for s in stacks]
+        feats = [run_head_stack_bf16(s[:-1], x, fused_bn) for s in stacks]
     groups, tails = [], []
-    for h, s, f in zip(names, stacks, feats):
+    for j, (h, s, f) in enumerate(zip(names, stacks, feats)):
         f = f.to(torch.bfloat16)
         if head_tail_takes_bf16(s[-1], f):
-            groups.append((_to_nhwc(f), s[-1].weight, s[-1].bias))
+            if whole is not None:  # one x for every group (head_tail_bf16 tells the tensors apart by identity): one input gradient
+                groups.append((whole_nhwc, s[-1].weight, s[-1].bias, j * width))
+            else:
+                groups.append((_to_nhwc(f), s[-1].weight, s[-1].bias))
             tails.append(h)
             ret[h] = None  # keeps the chain's key order
         else:
@@ -264,7 +295,7 @@ def _conv_module_bf16(conv, x):
     return y.permute(0, 3, 1, 2)
 
 
-def run_stack_bf16(modules, x):
+def run_stack_bf16(modules, x, fused_bn=False):
     """``modules(x)`` for a Sequential of ZeroPad2d, convolutions, BatchNorm2d and ReLU in mixed precision.  ``x`` is a bf16 device map,
     NCHW-shaped over NHWC memory (channels-last), and so is the result; no permuting copy in between.
 
@@ -274,7 +305,8 @@ def run_stack_bf16(modules, x):
       * any other convolution (stride 2 behind its ZeroPad2d, ConvTranspose2d): the module on an fp32 copy of its input, the result
         rounded to bf16;
       * BatchNorm2d: the sparse backbone's un-fused mixed-precision recipe -- bn(x.float()) with fp32 batch and running statistics, the
-        ReLU that follows, one rounding to bf16."""
+        ReLU that follows, one rounding to bf16; with ``fused_bn``, a module that dense_bn.batch_norm2d_nhwc_fusable accepts is one
+        batch_norm2d_act_nhwc call instead (relu=False where no ReLU follows)."""
     mods = list(modules.children())
     i = 0
     while i < len(mods):
@@ -290,13 +322,8 @@ def run_stack_bf16(modules, x):
             x = m(x.float()).to(torch.bfloat16)
             i += 1
         elif isinstance(m, nn.BatchNorm2d):
-            out = m(x.float())
-            if isinstance(nxt, nn.ReLU):
-                x = relu_to_bf16(out)
-                i += 2
-            else:
-                x = out.to(torch.bfloat16)
-                i += 1
+            x, used = _batch_norm_bf16(m, nxt, x, fused_bn)
+            i += used
         else:  # ZeroPad2d in front of a strided convolution, a ReLU on its own: exact on bf16
             x = m(x)
             i += 1

@@ -320,7 +320,7 @@ class CenterHead(nn.Module):
                                       forecast_feature=self.forecast_feature, wide_head=self.wide_head))
         self.compute_dtype = torch.float32
         self.fused_loss = False  # True: loss() of a standard / dense head runs on fd_loss.hip for fp32 maps on the device
-        self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the head runs on fd_dense_bn.hip (handed to the tasks)
+        self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the head runs on fd_dense_bn.hip, with train_dtype = bfloat16 on fd_dense_bn_nhwc.hip (handed to the tasks)
         self.train_dtype = torch.float32  # training: torch.bfloat16 = mixed precision on the bf16 NHWC convolutions (forward_mixed)
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
@@ -355,16 +355,22 @@ class CenterHead(nn.Module):
         SepHead are one dense_train.head_tail_bf16 call (fd_head_tail_bf16.hip) whose maps are fp32 NCHW.  ``feats`` and the
         forecast-feature concat stay bf16 in here; every returned map is fp32 and NCHW-contiguous, what loss() and the fused loss read.
         Layers the kernels do not take (bev_conv's 6- and 16-channel convolutions, more than 16 final channels) run their module on an
-        fp32 copy.  ``fused_bn`` has no effect here, as in RPN.forward_mixed."""
+        fp32 copy.
+
+        With ``fused_bn`` every BatchNorm2d (+ ReLU) that dense_bn.batch_norm2d_nhwc_fusable accepts runs on fd_dense_bn_nhwc.hip instead
+        (dense_bn.batch_norm2d_act_nhwc: bf16 channels-last in and out, fp32 statistics, no fp32 copy of the map), and the BatchNorm2d
+        modules of a SepHead's branches are ONE grouped call on the map of their batched convolution, of which the final convolutions
+        read their channel slices.  A frozen module and bev_conv's narrow layers keep the recipe above."""
         from .dense_train import run_head_stack_bf16, sep_head_bf16
 
-        x = run_head_stack_bf16(list(self.shared_conv.children()), x.to(torch.bfloat16, memory_format=torch.channels_last))
+        fused = bool(self.fused_bn)
+        x = run_head_stack_bf16(list(self.shared_conv.children()), x.to(torch.bfloat16, memory_format=torch.channels_last), fused)
         if self.bev_map:
-            x = x + run_head_stack_bf16(list(self.bev_conv.children()), bev_map.to(torch.bfloat16, memory_format=torch.channels_last))
+            x = x + run_head_stack_bf16(list(self.bev_conv.children()), bev_map.to(torch.bfloat16, memory_format=torch.channels_last), fused)
         ret_dicts = []
         for i, task in enumerate(self.tasks):
             xin = torch.cat([x, ret_dicts[i - 1]["feats"]], dim=1) if i != 0 and self.forecast_feature else x
-            ret_dicts.append(sep_head_bf16(task, xin))
+            ret_dicts.append(sep_head_bf16(task, xin, fused))
         if self.forecast_feature:
             ret_dicts = [dict((k, v.to(torch.float32, memory_format=torch.contiguous_format) if k == "feats" else v) for k, v in d.items())
                          for d in ret_dicts]

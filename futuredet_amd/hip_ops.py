@@ -1687,3 +1687,92 @@ def dense_bn_train_backward(dy, x, y, gamma, saved, relu=True):
     check(L.fd_dense_bn_train_backward(_p(dy), _p(x), _p(y), _p(gamma), _p(saved), b, c, p, int(bool(relu)), _p(dx), _p(dgamma), _p(dbeta),
                                        _p(ws), ws.numel(), _stream()), "fd_dense_bn_train_backward")
     return dx, dgamma, dbeta
+
+
+# ------------------------------------------------------------------------------------------------ dense BatchNorm on bf16 NHWC maps (training)
+def dense_bn_nhwc_chunk():
+    """Rows per chunk of the bf16 channels-last BatchNorm's sums (FD_DENSE_BN_NHWC_CHUNK): part of the summation order."""
+    return int(_lib.load().fd_dense_bn_nhwc_chunk())
+
+
+def dense_bn_nhwc_max_groups():
+    """BatchNorm2d modules one call of the bf16 channels-last BatchNorm takes (FD_DENSE_BN_NHWC_MAX_GROUPS)."""
+    return 8
+
+
+def dense_bn_nhwc_channels_ok(c):
+    return c % 32 == 0 and 32 <= c <= 512
+
+
+def _dense_bn_nhwc_rows(x, name):
+    """a contiguous bf16 [B, H, W, C] (or [n, C]) device tensor -> (tensor, n, C)"""
+    x = _dev(x, name, torch.bfloat16)
+    if x.dim() not in (2, 4):
+        raise FutureDetHipError("%s must be [B, H, W, C] or [n, C], got %s" % (name, tuple(x.shape)))
+    return x, x.numel() // x.shape[-1], x.shape[-1]
+
+
+def _dense_bn_nhwc_groups(bns, c, forward):
+    """the fd_dense_bn_nhwc_group array of the modules ``bns`` (their num_features partition the c channels)"""
+    bns = [bns] if isinstance(bns, torch.nn.Module) else list(bns)
+    if not 1 <= len(bns) <= dense_bn_nhwc_max_groups() or sum(int(bn.num_features) for bn in bns) != c:
+        raise FutureDetHipError("dense_bn_nhwc: needs 1 to %d BatchNorm2d modules whose num_features sum to the %d channels (got %s)"
+                                % (dense_bn_nhwc_max_groups(), c, [int(bn.num_features) for bn in bns]))
+    recs = []
+    for bn in bns:
+        gamma = _dev(bn.weight, "BatchNorm2d weight", torch.float32)
+        if forward:
+            for t, name in ((bn.bias, "bias"), (bn.running_mean, "running_mean"), (bn.running_var, "running_var")):
+                _dev(t, "BatchNorm2d " + name, torch.float32)
+            _dev(bn.num_batches_tracked, "BatchNorm2d num_batches_tracked", torch.int64)
+            if bn.momentum is None:
+                raise FutureDetHipError("dense_bn_nhwc: needs a fixed momentum (momentum=None is the cumulative average)")
+            recs.append(_lib.DenseBnNhwcGroup(gamma.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                                              bn.num_batches_tracked.data_ptr(), int(bn.num_features), float(bn.eps), float(bn.momentum)))
+        else:
+            recs.append(_lib.DenseBnNhwcGroup(gamma.data_ptr(), None, None, None, None, int(bn.num_features), float(bn.eps), 0.0))
+    return (_lib.DenseBnNhwcGroup * len(recs))(*recs), len(recs)
+
+
+def _dense_bn_nhwc_ws(L, n, c, device):
+    nbytes = L.fd_dense_bn_nhwc_workspace_bytes(int(n), int(c))
+    if nbytes == 0:
+        raise FutureDetHipError("dense_bn_nhwc: unsupported size: %d rows of %d channels (C a multiple of 32 in [32, 512], 2 <= n <= 2^30)" % (n, c))
+    return workspace.get("dense_bn_nhwc", nbytes, device)
+
+
+def dense_bn_nhwc_train_forward(x_nhwc, bns, relu=True):
+    """fd_dense_bn_nhwc_train_forward_bf16: y = act(gamma (x - mean) invstd + beta) on batch statistics over the rows of the contiguous
+    bf16 [B, H, W, C] tensor ``x_nhwc``.  ``bns``: one nn.BatchNorm2d or a list of at most 8 whose num_features partition the channels
+    (each a multiple of 32): each module's parameters, eps and momentum apply to its channels and its running_mean / running_var /
+    num_batches_tracked are updated in place on the device (their ``_version`` is NOT bumped: the caller does that).
+    Returns (y bf16 like x, saved fp32 [2, C] = mean, invstd).  Two launches, nothing is synchronised."""
+    L = _lib.load()
+    x, n, c = _dense_bn_nhwc_rows(x_nhwc, "x")
+    groups, ng = _dense_bn_nhwc_groups(bns, c, True)
+    ws = _dense_bn_nhwc_ws(L, n, c, x.device)
+    y = torch.empty_like(x)
+    saved = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    check(L.fd_dense_bn_nhwc_train_forward_bf16(_p(x), groups, ng, n, c, int(bool(relu)), _p(y), _p(saved), _p(ws), ws.numel(), _stream()),
+          "fd_dense_bn_nhwc_train_forward_bf16")
+    return y, saved
+
+
+def dense_bn_nhwc_train_backward(dy, x, y, saved, bns, relu=True):
+    """fd_dense_bn_nhwc_train_backward_bf16: -> (dx bf16 like x, dgamma fp32 [C], dbeta fp32 [C]; flat over the modules' channels).
+    ``y`` is the forward's output (the ReLU mask; may be None with relu=False), ``saved`` what the forward returned."""
+    L = _lib.load()
+    x, n, c = _dense_bn_nhwc_rows(x, "x")
+    dy = _dev(dy, "dy", torch.bfloat16)
+    if dy.shape != x.shape or (y is not None and _dev(y, "y", torch.bfloat16).shape != x.shape):
+        raise FutureDetHipError("dy and y must be %s" % (tuple(x.shape),))
+    if _dev(saved, "saved", torch.float32).numel() != 2 * c:
+        raise FutureDetHipError("saved does not hold %d channels" % c)
+    groups, ng = _dense_bn_nhwc_groups(bns, c, False)
+    ws = _dense_bn_nhwc_ws(L, n, c, x.device)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((c,), dtype=torch.float32, device=x.device)
+    dbeta = torch.empty((c,), dtype=torch.float32, device=x.device)
+    check(L.fd_dense_bn_nhwc_train_backward_bf16(_p(dy), _p(x), _p(y), _p(saved), groups, ng, n, c, int(bool(relu)), _p(dx), _p(dgamma),
+                                                 _p(dbeta), _p(ws), ws.numel(), _stream()), "fd_dense_bn_nhwc_train_backward_bf16")
+    return dx, dgamma, dbeta

@@ -71,6 +71,11 @@ class HeadTailGroup(ctypes.Structure):  # struct fd_head_tail_group
     _fields_ = [("x", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("y", c_void_p), ("x_stride", c_i64), ("cin", c_int), ("k", c_int)]
 
 
+class DenseBnNhwcGroup(ctypes.Structure):  # struct fd_dense_bn_nhwc_group
+    _fields_ = [("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p), ("num_batches_tracked", c_void_p),
+                ("c", c_int), ("eps", c_float), ("momentum", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -212,6 +217,14 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fd_dense_bn_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_int,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_dense_bn_nhwc_chunk": (c_int, []),
+    "fd_dense_bn_nhwc_stat_groups": (c_int, []),
+    "fd_dense_bn_nhwc_apply_blocks": (c_int, []),
+    "fd_dense_bn_nhwc_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "fd_dense_bn_nhwc_train_forward_bf16": (c_int, [c_void_p, ctypes.POINTER(DenseBnNhwcGroup), c_int, c_i64, c_int, c_int, c_void_p, c_void_p,
+                                                    c_void_p, c_size_t, c_void_p]),
+    "fd_dense_bn_nhwc_train_backward_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(DenseBnNhwcGroup), c_int, c_i64, c_int,
+                                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 for _name in ("fd_sparse_bn_train_forward", "fd_sparse_bn_train_backward"):  # bf16 rows: the same argument lists
     SIGNATURES[_name + "_bf16"] = SIGNATURES[_name]

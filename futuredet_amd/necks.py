@@ -57,6 +57,7 @@ class RPN(nn.Module):
         self.deblocks = nn.ModuleList(deblocks)
         self.compute_dtype = torch.float32
         self.fused_bn = False  # True: in .train() every fusable BatchNorm2d + ReLU of the blocks and deblocks runs on fd_dense_bn.hip
+                               # (with train_dtype = torch.bfloat16: on fd_dense_bn_nhwc.hip, bf16 channels-last)
         self.train_dtype = torch.float32  # training: torch.bfloat16 = mixed precision on the bf16 NHWC convolutions (forward_mixed)
         self._plan = None
         self.register_load_state_dict_post_hook(_drop_caches)
@@ -105,16 +106,19 @@ class RPN(nn.Module):
         channels-last, every block and deblock runs through dense_train.run_stack_bf16 -- the stride-1 3 x 3 convolutions and the
         1 x 1 deblock on fd_conv2d_nhwc_bf16 / fd_conv2d_wgrad_bf16 with fp32 master weights and fp32 weight gradients, BatchNorm with fp32
         statistics -- and the concatenated map is returned fp32 and NCHW-contiguous, which is what the head sees from forward_modules.
-        ``fused_bn`` has no effect here: fd_dense_bn.hip takes fp32 NCHW planes only (no NHWC / bf16 form yet), so BatchNorm2d runs the
-        backbone's un-fused recipe, bn(x.float()) + ReLU + one rounding."""
+        BatchNorm2d runs the backbone's un-fused recipe, bn(x.float()) + ReLU + one rounding; with ``fused_bn`` every module that
+        dense_bn.batch_norm2d_nhwc_fusable accepts (training mode, a multiple of 32 channels up to 512) runs with its ReLU on
+        fd_dense_bn_nhwc.hip instead (dense_bn.batch_norm2d_act_nhwc: bf16 channels-last in and out, fp32 statistics, no fp32 copy of the
+        map); a frozen module keeps the recipe."""
         from .dense_train import run_stack_bf16
 
+        fused = bool(self.fused_bn)
         x = x.to(torch.bfloat16, memory_format=torch.channels_last)
         ups = []
         for i in range(len(self.blocks)):
-            x = run_stack_bf16(self.blocks[i], x)
+            x = run_stack_bf16(self.blocks[i], x, fused)
             if i >= self.first_up:
-                ups.append(run_stack_bf16(self.deblocks[i - self.first_up], x))
+                ups.append(run_stack_bf16(self.deblocks[i - self.first_up], x, fused))
         if len(ups) > 0:
             x = torch.cat(ups, dim=1)
         return x.to(torch.float32, memory_format=torch.contiguous_format)

@@ -885,6 +885,53 @@ int fd_dense_bn_train_backward(const float *dy, const float *x, const float *y, 
                                int64_t P, int relu, float *dx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
                                fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mixed-precision training: BatchNorm2d on batch statistics over a bf16 channels-last map of the dense half, fused with the ReLU that
+ * follows it (fd_dense_bn_nhwc.hip).  Purely additive: fd_abi_version() stays 8.
+ * The map is rows x [n = B H W, C], bf16 (the bits, as uint16_t), row-major contiguous; C a multiple of 32 in [32, 512]; n in [2, 2^30];
+ * relu 0 or 1.  y, dy and dx are bf16 rows like x: a row is widened exactly on load and rounded once, to nearest even (a NaN stays a NaN),
+ * on store.  saved [2, C], dgamma [C], dbeta [C], the parameters, the running statistics and the workspace are fp32.
+ * One call serves the channel ranges of up to FD_DENSE_BN_NHWC_MAX_GROUPS BatchNorm2d modules: record j of `groups`
+ * (fd_dense_bn_nhwc_group, read on the host and passed to the kernels by value) owns the next c channels -- c a multiple of 32, the c
+ * of all records summing to C -- with its own gamma [c], beta [c], eps, momentum, running_mean [c], running_var [c] and counter.
+ *   forward:  y = act(gamma (x - mean) invstd + beta);  mean and the biased variance over the n rows, invstd = 1 / sqrt(var + eps) with
+ *             the record's eps;  saved = [mean[C], invstd[C]];  per record running_mean <- (1 - momentum) running_mean + momentum mean,
+ *             running_var the same with the unbiased variance var n / (n - 1), num_batches_tracked (int64) += 1 -- all on the device.
+ *   backward: g = dy where y > 0 (relu = 1; y is the forward's output) or dy;  dbeta = sum g;  dgamma = sum g x^,
+ *             x^ = (x - mean) invstd;  dx = gamma invstd (g - dbeta / n - x^ dgamma / n).  Reads only gamma of a record.
+ * Sums: the design of fd_sparse_bn.hip.  Rows are cut into chunks of fd_dense_bn_nhwc_chunk() (= FD_DENSE_BN_NHWC_CHUNK) rows;
+ * consecutive chunks form at most fd_dense_bn_nhwc_stat_groups() groups; a chunk's partial is centred at the chunk's own mean; partials are
+ * combined in double, in a fixed order, with Chan's rule.  The element-wise passes cut the rows into at most
+ * fd_dense_bn_nhwc_apply_blocks() blocks of whole chunks.  No atomics, and every boundary follows from (n, C): the same bits on every run.
+ * Two launches per call; no allocation, no synchronisation.  workspace >= fd_dense_bn_nhwc_workspace_bytes(n, C) (0 = unsupported
+ * sizes), 16-byte aligned; it need not be initialised and the backward does not need the forward's contents.
+ * Both entry points validate on the host before any device work; FD_EINVAL for: a null pointer (other than y when relu = 0, and in the
+ * backward every member of a record but gamma), C or a record's c out of range or no multiple of 32, c not summing to C, n_groups
+ * outside [1, FD_DENSE_BN_NHWC_MAX_GROUPS], n outside [2, 2^30], relu not 0 or 1, (forward) a record's eps <= 0 or momentum outside
+ * [0, 1], a workspace that is null, too small or misaligned, x, y, dy, dx or saved not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_DENSE_BN_NHWC_CHUNK 256
+#define FD_DENSE_BN_NHWC_MAX_GROUPS 8
+#define FD_DENSE_BN_NHWC_STAT_GROUPS 256
+#define FD_DENSE_BN_NHWC_APPLY_BLOCKS 512
+typedef struct fd_dense_bn_nhwc_group {
+    const float *gamma, *beta;
+    float *running_mean, *running_var;
+    int64_t *num_batches_tracked;
+    int c;
+    float eps;
+    double momentum;
+} fd_dense_bn_nhwc_group;
+int fd_dense_bn_nhwc_chunk(void);
+int fd_dense_bn_nhwc_stat_groups(void);
+int fd_dense_bn_nhwc_apply_blocks(void);
+size_t fd_dense_bn_nhwc_workspace_bytes(int64_t n, int C);
+int fd_dense_bn_nhwc_train_forward_bf16(const uint16_t *x, const fd_dense_bn_nhwc_group *groups, int n_groups, int64_t n, int C, int relu,
+                                        uint16_t *y, float *saved, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_dense_bn_nhwc_train_backward_bf16(const uint16_t *dy, const uint16_t *x, const uint16_t *y, const float *saved,
+                                         const fd_dense_bn_nhwc_group *groups, int n_groups, int64_t n, int C, int relu, uint16_t *dx,
+                                         float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
