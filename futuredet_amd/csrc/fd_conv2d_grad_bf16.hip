@@ -20,6 +20,9 @@
 // of 4 pixels x 16 channels, delivered channel-major).  The 4 pixels x 32 channels that a 32-lane half reads are 256 contiguous
 // bytes, one bank row: conflict free, and a k-step or the second half of a fragment is an immediate offset from one per-lane base.
 //
+// The layers that change resolution (3 x 3 / stride 2, the 2 x 2 / stride 2 pair) take their weight gradient from the same kernel
+// template with another staging address: fd_conv2d_wgrad_s2_bf16 and fd_conv2d_wgrad_2x2_bf16 at the end of this file.
+//
 // Out-of-image taps: the x image of kernel column kx holds, AT THE INDEX OF THE OUTPUT PIXEL p, the input pixel that tap (ky, kx)
 // reads for p -- or zeros when that pixel lies outside the image (a zero halo written by the staging, one image per kx; ky is fixed
 // per workgroup).  Pixels past the end of the chunk are zeros in every image.  The MFMA loop has no branch and no mask.
@@ -75,8 +78,9 @@ __global__ void __launch_bounds__(256) conv2d_pack_weight_dev(const float *__res
 
 // ---------------------------------------------------------------------------------------------------------------- weight gradient
 struct WgradParams {
-    int H, W, cin, cout;
-    int n_pix;     // B * H * W
+    int H, W, cin, cout;  // H x W: the map x
+    int Ho, Wo;           // the map dy (stride 1: H x W)
+    int n_pix;            // B * Ho * Wo
     int n_chunks;
 };
 
@@ -97,10 +101,14 @@ __device__ __forceinline__ bf16x8 read_frag(const unsigned char *base, int byte_
 }
 
 // grid: (chunk, kernel row ky, (cin / 32) * ceil(cout / 128)); LDS: KS x images + kCoBlocks dy images of kImgB bytes
-template <int KS>
+//
+// ONE template for every geometry, not a copy per layer kind: the stride S and the padding PAD enter the staging address only -- the x
+// image of tap (ky, kx) holds, at the index of dy pixel (oy, ox), the x pixel (S oy + ky - PAD, S ox + kx - PAD) or zeros.  <3, 1, 1> and
+// <1, 1, 0> are the stride-1 layers (their address arithmetic and every addition are what they were); <3, 2, 1> is the 3 x 3 / stride 2
+// / padding 1 layer; <2, 2, 0> is the 2 x 2 / stride 2 pair, x the fine map and dy the coarse one (fd_conv2d_strided_grad_bf16.hip).
+template <int KS, int S, int PAD>
 __global__ void __launch_bounds__(256) conv2d_wgrad_partial(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, WgradParams p,
                                                             float *__restrict__ partial) {
-    constexpr int PAD = KS / 2;
     constexpr int NX = kBatch * 4 / 256;              // 16-byte pieces of one x image per thread
     constexpr int NY = kBatch * 4 * kCoBlocks / 256;  // ... of the dy images
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -114,8 +122,8 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_partial(const unsigned short
     const int p0 = chunk * kChunk;
     const int n = min(kChunk, p.n_pix - p0);  // >= 1: the host launches ceil(n_pix / kChunk) chunks
     const int n_batches = (n + kBatch - 1) / kBatch;
-    const int HW = p.H * p.W;
-    const int row_shift = (ky - PAD) * p.W;
+    const int HW = p.Ho * p.Wo;
+    const int row_shift = (ky - PAD) * p.W;  // (stride 1)
 
     uint4 rx[KS][NX], ry[NY];
     auto load_batch = [&](int bt) {
@@ -125,13 +133,17 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_partial(const unsigned short
             const int id = tid + i * 256, pix = id >> 2, q = id & 3;
             const int pp = p0 + b0 + pix;  // the OUTPUT pixel this slot belongs to
             const bool have = b0 + pix < n;
-            const int rem = pp % HW, yy = rem / p.W, xx = rem - yy * p.W;
-            const bool row_ok = have && (unsigned)(yy + ky - PAD) < (unsigned)p.H;
+            const int rem = pp % HW, yy = rem / p.Wo, xx = rem - yy * p.Wo;
+            const int iy = S * yy + ky - PAD;
+            const bool row_ok = have && (unsigned)iy < (unsigned)p.H;
+            // stride 1: x and dy share their pixel index; otherwise the x pixel is addressed by (map, row, column)
+            const int64_t row0 = S == 1 ? (int64_t)(pp + row_shift - xx) : ((int64_t)(pp / HW) * p.H + iy) * p.W;
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
+                const int ix = S * xx + kx - PAD;
                 rx[kx][i] = make_uint4(0u, 0u, 0u, 0u);
-                if (row_ok && (unsigned)(xx + kx - PAD) < (unsigned)p.W)
-                    rx[kx][i] = *reinterpret_cast<const uint4 *>(x + (int64_t)(pp + row_shift + kx - PAD) * p.cin + cib * 32 + q * 8);
+                if (row_ok && (unsigned)ix < (unsigned)p.W)
+                    rx[kx][i] = *reinterpret_cast<const uint4 *>(x + (row0 + ix) * p.cin + cib * 32 + q * 8);
             }
         }
 #pragma unroll
@@ -200,8 +212,9 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_partial(const unsigned short
     }
 }
 
-// dw[co][ci][tap] = sum over chunks, in chunk order, of partial[chunk][tap][ci][co]
-__global__ void __launch_bounds__(256) conv2d_wgrad_reduce(const float *__restrict__ partial, int taps, int cin, int cout, int n_chunks, float *__restrict__ dw) {
+// dw[co][ci][tap] (ci_major: dw[ci][co][tap]) = sum over chunks, in chunk order, of partial[chunk][tap][ci][co]
+__global__ void __launch_bounds__(256) conv2d_wgrad_reduce(const float *__restrict__ partial, int taps, int cin, int cout, int n_chunks, int ci_major,
+                                                           float *__restrict__ dw) {
     const int64_t total = (int64_t)taps * cin * cout;
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (tap, ci, co), co fastest: coalesced reads
     if (e >= total) return;
@@ -210,7 +223,27 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_reduce(const float *__restri
     const int co = (int)(e % cout);
     const int64_t t = e / cout;
     const int ci = (int)(t % cin), tap = (int)(t / cin);
-    dw[((int64_t)co * cin + ci) * taps + tap] = s;
+    dw[(ci_major ? (int64_t)ci * cout + co : (int64_t)co * cin + ci) * taps + tap] = s;
+}
+
+// the two launches of a weight gradient; p is complete and the workspace large enough
+template <int KS, int S, int PAD>
+void launch_wgrad(const void *x, const void *dy, const WgradParams &p, float *partial, int ci_major, float *dw, hipStream_t s) {
+    const int n_cog = (p.cout + 32 * kCoBlocks - 1) / (32 * kCoBlocks);
+    const dim3 grid((unsigned)p.n_chunks, (unsigned)KS, (unsigned)((p.cin / 32) * n_cog));
+    const size_t lds = (size_t)(KS + kCoBlocks) * kImgB;  // 56 KB for 3 x 3: two workgroups per compute unit
+    hipLaunchKernelGGL((conv2d_wgrad_partial<KS, S, PAD>), grid, dim3(256), lds, s, (const unsigned short *)x, (const unsigned short *)dy, p, partial);
+    const int64_t total = (int64_t)KS * KS * p.cin * p.cout;
+    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, partial, KS * KS, p.cin, p.cout, p.n_chunks, ci_major,
+                       dw);
+}
+
+int64_t channel_blocks(int cin, int cout) { return (int64_t)(cin / 32) * ((cout + 32 * kCoBlocks - 1) / (32 * kCoBlocks)); }
+
+// chunks of dy pixels, or 0 where the shapes are not served
+int64_t wgrad_chunks(int64_t B, int64_t Ho, int64_t Wo, int cin, int cout) {
+    if (B <= 0 || Ho <= 0 || Wo <= 0 || cin <= 0 || cout <= 0 || cin % 32 || cout % 32) return 0;
+    return (B * Ho * Wo + kChunk - 1) / kChunk;
 }
 
 }  // namespace
@@ -249,19 +282,61 @@ extern "C" int fd_conv2d_wgrad_bf16(const void *x, const void *dy, int B, int H,
     const size_t need = fd_conv2d_wgrad_bf16_workspace_bytes(B, H, W, cin, cout, ks);
     FD_REQUIRE(workspace_bytes >= need, "fd_conv2d_wgrad_bf16: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
     WgradParams p;
-    p.H = H; p.W = W; p.cin = cin; p.cout = cout;
+    p.H = p.Ho = H; p.W = p.Wo = W; p.cin = cin; p.cout = cout;
     p.n_pix = (int)n_pix;
     p.n_chunks = (int)((n_pix + kChunk - 1) / kChunk);
-    const int n_cog = (cout + 32 * kCoBlocks - 1) / (32 * kCoBlocks);
-    const int64_t gz = (int64_t)(cin / 32) * n_cog;
-    FD_REQUIRE(gz <= 65535, "fd_conv2d_wgrad_bf16: too many channel blocks (%d -> %d)", cin, cout);
+    FD_REQUIRE(channel_blocks(cin, cout) <= 65535, "fd_conv2d_wgrad_bf16: too many channel blocks (%d -> %d)", cin, cout);
     hipStream_t s = fd::as_stream(stream);
-    float *partial = (float *)workspace;
-    const dim3 grid((unsigned)p.n_chunks, (unsigned)ks, (unsigned)gz);
-    const size_t lds = (size_t)(ks + kCoBlocks) * kImgB;  // 56 KB for 3 x 3: two workgroups per compute unit
-    if (ks == 3) hipLaunchKernelGGL(conv2d_wgrad_partial<3>, grid, dim3(256), lds, s, (const unsigned short *)x, (const unsigned short *)dy, p, partial);
-    else hipLaunchKernelGGL(conv2d_wgrad_partial<1>, grid, dim3(256), lds, s, (const unsigned short *)x, (const unsigned short *)dy, p, partial);
-    const int64_t total = (int64_t)ks * ks * cin * cout;
-    hipLaunchKernelGGL(conv2d_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, partial, ks * ks, cin, cout, p.n_chunks, dw);
+    if (ks == 3) launch_wgrad<3, 1, 1>(x, dy, p, (float *)workspace, 0, dw, s);
+    else launch_wgrad<1, 1, 0>(x, dy, p, (float *)workspace, 0, dw, s);
     return fd::check_launch("fd_conv2d_wgrad_bf16");
+}
+
+// ---- the strided layers (include/futuredet_hip.h; the kernels around them: fd_conv2d_strided_grad_bf16.hip).  They live here because
+// they are instantiations of conv2d_wgrad_partial, not kernels of their own.
+extern "C" size_t fd_conv2d_wgrad_s2_bf16_workspace_bytes(int B, int H, int W, int cin, int cout) {
+    if (H <= 0 || W <= 0) return 0;
+    return (size_t)wgrad_chunks(B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, cin, cout) * 9 * cin * cout * sizeof(float);
+}
+
+extern "C" int fd_conv2d_wgrad_s2_bf16(const void *x, const void *dy, int B, int H, int W, int cin, int cout, void *workspace, size_t workspace_bytes,
+                                       float *dw, fd_stream_t stream) {
+    FD_REQUIRE(x && dy && dw && workspace, "fd_conv2d_wgrad_s2_bf16: null argument");
+    FD_REQUIRE(cin > 0 && cout > 0 && cin % 32 == 0 && cout % 32 == 0,
+               "fd_conv2d_wgrad_s2_bf16: cin and cout must be positive multiples of 32 (got %d -> %d)", cin, cout);
+    FD_REQUIRE(B > 0 && H > 0 && W > 0, "fd_conv2d_wgrad_s2_bf16: bad shape %d x %d x %d", B, H, W);
+    WgradParams p;
+    p.H = H; p.W = W; p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1; p.cin = cin; p.cout = cout;
+    FD_REQUIRE((int64_t)B * H * W + kChunk < (1ll << 31), "fd_conv2d_wgrad_s2_bf16: maps of 2^31 pixels and more are not supported");
+    const size_t need = fd_conv2d_wgrad_s2_bf16_workspace_bytes(B, H, W, cin, cout);
+    FD_REQUIRE(workspace_bytes >= need, "fd_conv2d_wgrad_s2_bf16: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
+    p.n_pix = B * p.Ho * p.Wo;
+    p.n_chunks = (p.n_pix + kChunk - 1) / kChunk;
+    FD_REQUIRE(channel_blocks(cin, cout) <= 65535, "fd_conv2d_wgrad_s2_bf16: too many channel blocks (%d -> %d)", cin, cout);
+    launch_wgrad<3, 2, 1>(x, dy, p, (float *)workspace, 0, dw, fd::as_stream(stream));
+    return fd::check_launch("fd_conv2d_wgrad_s2_bf16");
+}
+
+extern "C" size_t fd_conv2d_wgrad_2x2_bf16_workspace_bytes(int B, int H, int W, int c_coarse, int c_fine) {
+    if (H < 2 || W < 2) return 0;
+    return (size_t)wgrad_chunks(B, H / 2, W / 2, c_fine, c_coarse) * 4 * c_fine * c_coarse * sizeof(float);
+}
+
+extern "C" int fd_conv2d_wgrad_2x2_bf16(const void *coarse, const void *fine, int B, int H, int W, int c_coarse, int c_fine, int fine_major,
+                                        void *workspace, size_t workspace_bytes, float *dw, fd_stream_t stream) {
+    FD_REQUIRE(coarse && fine && dw && workspace, "fd_conv2d_wgrad_2x2_bf16: null argument");
+    FD_REQUIRE(fine_major == 0 || fine_major == 1, "fd_conv2d_wgrad_2x2_bf16: fine_major must be 0 or 1 (got %d)", fine_major);
+    FD_REQUIRE(c_coarse > 0 && c_fine > 0 && c_coarse % 32 == 0 && c_fine % 32 == 0,
+               "fd_conv2d_wgrad_2x2_bf16: both channel counts must be positive multiples of 32 (got %d coarse, %d fine)", c_coarse, c_fine);
+    FD_REQUIRE(B > 0 && H >= 2 && W >= 2, "fd_conv2d_wgrad_2x2_bf16: bad shape %d x %d x %d (the fine map; 2 x 2 at least)", B, H, W);
+    FD_REQUIRE((int64_t)B * H * W + kChunk < (1ll << 31), "fd_conv2d_wgrad_2x2_bf16: maps of 2^31 pixels and more are not supported");
+    const size_t need = fd_conv2d_wgrad_2x2_bf16_workspace_bytes(B, H, W, c_coarse, c_fine);
+    FD_REQUIRE(workspace_bytes >= need, "fd_conv2d_wgrad_2x2_bf16: workspace too small (%zu bytes, need %zu)", workspace_bytes, need);
+    WgradParams p;  // x = the fine map (M = its channels), dy = the coarse map: partial [tap][fine channel][coarse channel]
+    p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2; p.cin = c_fine; p.cout = c_coarse;
+    p.n_pix = B * p.Ho * p.Wo;
+    p.n_chunks = (p.n_pix + kChunk - 1) / kChunk;
+    FD_REQUIRE(channel_blocks(c_fine, c_coarse) <= 65535, "fd_conv2d_wgrad_2x2_bf16: too many channel blocks (%d, %d)", c_coarse, c_fine);
+    launch_wgrad<2, 2, 0>(fine, coarse, p, (float *)workspace, fine_major, dw, fd::as_stream(stream));
+    return fd::check_launch("fd_conv2d_wgrad_2x2_bf16");
 }

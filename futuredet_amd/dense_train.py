@@ -1,6 +1,8 @@
-"""Mixed-precision training of the dense stride-1 convolutions (the RPN neck, the CenterHead) on the bf16 NHWC kernels: the autograd
-surfaces (conv2d_bf16; head_tail_bf16 for the head's final convolutions), the predicates that say where they apply (conv_takes_bf16 for
-the neck, head_conv_takes_bf16 / head_tail_takes_bf16 for the head), and the walk over a ZeroPad2d / Conv2d / BatchNorm2d / ReLU
+"""Mixed-precision training of the dense convolutions (the RPN neck, the CenterHead) on the bf16 NHWC kernels: the autograd
+surfaces (conv2d_bf16 for stride 1; conv2d_s2_bf16, conv_transpose2d_k2_bf16 and conv2d_k2s2_bf16 for the neck's layers that change
+resolution; head_tail_bf16 for the head's final convolutions), the predicates that say where they apply (conv_takes_bf16,
+conv_s2_takes_bf16, conv_up2_takes_bf16 and conv_down2_takes_bf16 for the neck, head_conv_takes_bf16 / head_tail_takes_bf16 for the
+head), and the walk over a ZeroPad2d / Conv2d / BatchNorm2d / ReLU
 stack that RPN.train_dtype = torch.bfloat16 switches on (run_stack_bf16).  The recipe is the sparse backbone's: bf16 activations, fp32
 master weights packed to bf16 on the device every step, fp32 accumulation, fp32 weight gradients and BatchNorm statistics.  With
 ``fused_bn`` the walks hand every BatchNorm2d (+ ReLU) that dense_bn.batch_norm2d_nhwc_fusable accepts to
@@ -74,6 +76,125 @@ def conv2d_bf16(x_nhwc, weight, ks, bias=None):
         raise hip_ops.FutureDetHipError("conv2d_bf16: needs an fp32 [%d] bias on x's device (got %s %s)"
                                         % (weight.shape[0], tuple(bias.shape), bias.dtype))
     return _Conv2dBf16Function.apply(x_nhwc, weight.contiguous(), ks, bias.contiguous())
+
+
+class _Conv2dS2Bf16Function(torch.autograd.Function):
+    """The 3 x 3 / stride 2 / padding 1 convolution on x [B, H, W, Cin] bf16 with the fp32 OIHW weight.
+
+    forward:  fd_conv2d_pack_weight_dev (mode 0) + fd_conv2d_nhwc_bf16 with stride 2;
+    backward: dX on fd_conv2d_s2_dgrad_bf16 (the mode-1 pack; four parity phases, 9 taps per 2 x 2 block of dX);
+              dW on fd_conv2d_wgrad_s2_bf16, fp32.  Saves the inputs only; nothing reads a value back to the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        y = hip_ops.conv2d_nhwc_bf16(x, hip_ops.pack_conv2d_weight_device(weight), None, weight.shape[0], 3, stride=2, relu=False)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.to(torch.bfloat16).contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = hip_ops.conv2d_s2_dgrad_bf16(dy, hip_ops.pack_conv2d_weight_device(weight, transposed=True), x.shape[1], x.shape[2], x.shape[3])
+        if ctx.needs_input_grad[1]:
+            dw = hip_ops.conv2d_wgrad_s2_bf16(x, dy)
+        return dx, dw
+
+
+class _ConvTranspose2dK2Bf16Function(torch.autograd.Function):
+    """ConvTranspose2d(kernel 2, stride 2) on x [B, H, W, Cin] bf16 with the fp32 [Cin, Cout, 2, 2] weight: x is the coarse map.
+
+    forward:  up2 (fd_conv2d_pack_weight_2x2_dev + four placed 1 x 1 launches of fd_conv2d_nhwc_bf16);
+    backward: dX = down2 of dY (fd_conv2d_down2_bf16); dW on fd_conv2d_wgrad_2x2_bf16, fp32.  Saves the inputs only."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        y = hip_ops.conv2d_up2_bf16(x, hip_ops.pack_conv2d_weight_2x2_device(weight, hip_ops.PACK_UP2), weight.shape[1])
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.to(torch.bfloat16).contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = hip_ops.conv2d_down2_bf16(dy, hip_ops.pack_conv2d_weight_2x2_device(weight, hip_ops.PACK_DOWN2), weight.shape[0])
+        if ctx.needs_input_grad[1]:
+            dw = hip_ops.conv2d_wgrad_2x2_bf16(x, dy)
+        return dx, dw
+
+
+class _Conv2dK2S2Bf16Function(torch.autograd.Function):
+    """Conv2d(kernel 2, stride 2) on x [B, H, W, Cin] bf16 with the fp32 [Cout, Cin, 2, 2] weight: x is the fine map.
+
+    forward:  down2 (fd_conv2d_pack_weight_2x2_dev + fd_conv2d_down2_bf16);
+    backward: dX = up2 of dY; for an odd H or W it lands in a zero-filled map, whose trailing row or column no output read;
+              dW on fd_conv2d_wgrad_2x2_bf16, fp32.  Saves the inputs only."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        y = hip_ops.conv2d_down2_bf16(x, hip_ops.pack_conv2d_weight_2x2_device(weight, hip_ops.PACK_DOWN2), weight.shape[0])
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = dy.to(torch.bfloat16).contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = hip_ops.conv2d_up2_bf16(dy, hip_ops.pack_conv2d_weight_2x2_device(weight, hip_ops.PACK_UP2), weight.shape[1])
+            if tuple(dx.shape) != tuple(x.shape):  # (the placed launches address a map of exactly twice the coarse size)
+                full = torch.zeros_like(x)
+                full[:, :dx.shape[1], :dx.shape[2]] = dx
+                dx = full
+        if ctx.needs_input_grad[1]:
+            dw = hip_ops.conv2d_wgrad_2x2_bf16(dy, x)
+        return dx, dw
+
+
+def _strided_args(name, x_nhwc, weight, kernel, cin_axis, min_hw):
+    """the checks the three strided functions share: x a contiguous bf16 [B, H, W, Cin] device map of at least min_hw x min_hw pixels,
+    weight fp32 [., ., kernel, kernel] on its device with Cin on ``cin_axis``, both channel counts multiples of 32"""
+    if not (isinstance(x_nhwc, torch.Tensor) and x_nhwc.is_cuda and x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4
+            and x_nhwc.is_contiguous()):
+        raise hip_ops.FutureDetHipError("%s: x must be a contiguous bf16 [B, H, W, Cin] tensor on the HIP device" % name)
+    if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.device == x_nhwc.device and weight.dim() == 4
+            and tuple(weight.shape[2:]) == (kernel, kernel) and weight.shape[cin_axis] == x_nhwc.shape[3] and weight.shape[0] % 32 == 0
+            and weight.shape[1] % 32 == 0 and min(x_nhwc.shape[1], x_nhwc.shape[2]) >= min_hw):
+        raise hip_ops.FutureDetHipError("%s: needs an fp32 [%s, %d, %d] weight on x's device with Cin = %d, both channel counts multiples of 32, "
+                                        "and a map of %d x %d pixels at least (got %s %s, x %s)"
+                                        % (name, "Cout, Cin" if cin_axis == 1 else "Cin, Cout", kernel, kernel, x_nhwc.shape[3], min_hw, min_hw,
+                                           tuple(weight.shape), weight.dtype, tuple(x_nhwc.shape)))
+
+
+def conv2d_s2_bf16(x_nhwc, weight):
+    """y [B, (H-1)//2+1, (W-1)//2+1, Cout] bf16 = the 3 x 3 / stride 2 / padding 1 convolution of x [B, H, W, Cin] (bf16, contiguous, on the
+    device) with ``weight``, the module's fp32 [Cout, Cin, 3, 3] parameter.  Differentiable in x and weight.  Raises where the kernels do
+    not apply: there is no fallback here."""
+    _strided_args("conv2d_s2_bf16", x_nhwc, weight, 3, 1, 1)
+    return _Conv2dS2Bf16Function.apply(x_nhwc, weight.contiguous())
+
+
+def conv_transpose2d_k2_bf16(x_nhwc, weight):
+    """y [B, 2H, 2W, Cout] bf16 = ConvTranspose2d(kernel 2, stride 2) of x [B, H, W, Cin] (bf16, contiguous, on the device) with ``weight``,
+    the module's fp32 [Cin, Cout, 2, 2] parameter.  Differentiable in x and weight.  Raises where the kernels do not apply."""
+    _strided_args("conv_transpose2d_k2_bf16", x_nhwc, weight, 2, 0, 1)
+    return _ConvTranspose2dK2Bf16Function.apply(x_nhwc, weight.contiguous())
+
+
+def conv2d_k2s2_bf16(x_nhwc, weight):
+    """y [B, H//2, W//2, Cout] bf16 = Conv2d(kernel 2, stride 2, padding 0) of x [B, H, W, Cin] (bf16, contiguous, on the device) with
+    ``weight``, the module's fp32 [Cout, Cin, 2, 2] parameter.  The trailing row or column of an odd H or W is not read and its gradient is
+    exactly zero.  Differentiable in x and weight.  Raises where the kernels do not apply."""
+    _strided_args("conv2d_k2s2_bf16", x_nhwc, weight, 2, 1, 2)
+    return _Conv2dK2S2Bf16Function.apply(x_nhwc, weight.contiguous())
 
 
 class _HeadTailBf16Function(torch.autograd.Function):
@@ -289,6 +410,44 @@ def _pad_then_conv_takes_bf16(pad, conv, x):
     return isinstance(pad, nn.ZeroPad2d) and tuple(pad.padding) == (1, 1, 1, 1) and _conv_takes(conv, x, {1: None, 3: 0})
 
 
+def _strided_takes(conv, x, cls, kernel, padding):
+    """a ``cls`` module of kernel size ``kernel``, stride 2 and ``padding`` on every side: no bias, groups 1, dilation 1, zero padding, an
+    fp32 weight on x's device, both channel counts multiples of 32"""
+    return (isinstance(conv, cls) and conv.kernel_size == (kernel, kernel) and conv.stride == (2, 2) and tuple(conv.padding) == (padding, padding)
+            and conv.padding_mode == "zeros" and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and tuple(getattr(conv, "output_padding", (0, 0))) == (0, 0) and conv.in_channels % 32 == 0 and conv.out_channels % 32 == 0
+            and conv.weight.dtype == torch.float32 and conv.weight.device == x.device)
+
+
+def conv_s2_takes_bf16(conv, x):
+    """True where conv2d_s2_bf16 can take the place of ``conv`` on the map ``x``: an nn.Conv2d with a 3 x 3 kernel, stride 2 and padding 1,
+    dilation 1, groups 1, no bias, in_channels and out_channels multiples of 32, an fp32 weight on x's device."""
+    return _strided_takes(conv, x, nn.Conv2d, 3, 1)
+
+
+def _pad_then_conv_s2_takes_bf16(pad, conv, x):
+    """nn.ZeroPad2d(1) + a 3 x 3 / padding 0 / stride 2 convolution that otherwise satisfies conv_s2_takes_bf16: together one 3 x 3 /
+    stride 2 / padding 1 (the eval plan merges them the same way)."""
+    return isinstance(pad, nn.ZeroPad2d) and tuple(pad.padding) == (1, 1, 1, 1) and _strided_takes(conv, x, nn.Conv2d, 3, 0)
+
+
+def conv_up2_takes_bf16(conv, x):
+    """True where conv_transpose2d_k2_bf16 can take the place of ``conv``: an nn.ConvTranspose2d with a 2 x 2 kernel, stride 2, no padding
+    or output padding, dilation 1, groups 1, no bias, both channel counts multiples of 32, an fp32 weight on x's device."""
+    return _strided_takes(conv, x, nn.ConvTranspose2d, 2, 0)
+
+
+def conv_down2_takes_bf16(conv, x):
+    """True where conv2d_k2s2_bf16 can take the place of ``conv``: an nn.Conv2d with a 2 x 2 kernel, stride 2 and padding 0, dilation 1,
+    groups 1, no bias, both channel counts multiples of 32, an fp32 weight on x's device, on a map of 2 x 2 pixels at least."""
+    return _strided_takes(conv, x, nn.Conv2d, 2, 0) and x.dim() == 4 and min(x.shape[2], x.shape[3]) >= 2
+
+
+def _strided_module_bf16(fn, conv, x):
+    """``conv`` through one of the strided functions on an NCHW-shaped view of NHWC memory; returns the same kind of view"""
+    return fn(x.permute(0, 2, 3, 1).contiguous(), conv.weight).permute(0, 3, 1, 2)  # (no copy for a channels-last map)
+
+
 def _conv_module_bf16(conv, x):
     """``conv`` through conv2d_bf16 on an NCHW-shaped view of NHWC memory; returns the same kind of view"""
     y = conv2d_bf16(x.permute(0, 2, 3, 1).contiguous(), conv.weight, conv.kernel_size[0])  # (no copy for a channels-last map)
@@ -302,8 +461,14 @@ def run_stack_bf16(modules, x, fused_bn=False):
       * nn.ZeroPad2d(1) directly followed by a 3 x 3 / padding 0 / stride 1 convolution that otherwise satisfies conv_takes_bf16: the
         pair is one conv2d_bf16 call (the eval plan merges them the same way);
       * a convolution that satisfies conv_takes_bf16: conv2d_bf16;
-      * any other convolution (stride 2 behind its ZeroPad2d, ConvTranspose2d): the module on an fp32 copy of its input, the result
-        rounded to bf16;
+      * nn.ZeroPad2d(1) directly followed by a 3 x 3 / padding 0 / stride 2 convolution (_pad_then_conv_s2_takes_bf16), or a convolution
+        that satisfies conv_s2_takes_bf16 -- the opener of a down-sampling stage: conv2d_s2_bf16;
+      * an nn.ConvTranspose2d(2, stride 2) that satisfies conv_up2_takes_bf16: conv_transpose2d_k2_bf16;
+      * any other convolution (a bias, other kernel sizes or strides, channel counts that are no multiples of 32): the module on an
+        fp32 copy of its input, the result rounded to bf16.  The nn.Conv2d(2, stride 2) deblock of the PointPillars neck is among them
+        although conv2d_k2s2_bf16 can run it (conv_down2_takes_bf16): at its shipped shape its forward + backward was not faster than
+        this recipe by more than the recipe's own spread (229 us against 245 us, profiles/dense_conv_strided_bf16.txt), so the walk does
+        not route it;
       * BatchNorm2d: the sparse backbone's un-fused mixed-precision recipe -- bn(x.float()) with fp32 batch and running statistics, the
         ReLU that follows, one rounding to bf16; with ``fused_bn``, a module that dense_bn.batch_norm2d_nhwc_fusable accepts is one
         batch_norm2d_act_nhwc call instead (relu=False where no ReLU follows)."""
@@ -318,13 +483,22 @@ def run_stack_bf16(modules, x, fused_bn=False):
         elif conv_takes_bf16(m, x):
             x = _conv_module_bf16(m, x)
             i += 1
+        elif nxt is not None and _pad_then_conv_s2_takes_bf16(m, nxt, x):
+            x = _strided_module_bf16(conv2d_s2_bf16, nxt, x)
+            i += 2
+        elif conv_s2_takes_bf16(m, x):
+            x = _strided_module_bf16(conv2d_s2_bf16, m, x)
+            i += 1
+        elif conv_up2_takes_bf16(m, x):
+            x = _strided_module_bf16(conv_transpose2d_k2_bf16, m, x)
+            i += 1
         elif isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
             x = m(x.float()).to(torch.bfloat16)
             i += 1
         elif isinstance(m, nn.BatchNorm2d):
             x, used = _batch_norm_bf16(m, nxt, x, fused_bn)
             i += used
-        else:  # ZeroPad2d in front of a strided convolution, a ReLU on its own: exact on bf16
+        else:  # ZeroPad2d in front of a convolution that stays on torch, a ReLU on its own: exact on bf16
             x = m(x)
             i += 1
     return x

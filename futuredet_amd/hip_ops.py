@@ -586,6 +586,130 @@ def conv2d_wgrad_bf16(x_nhwc, dy_nhwc, ks):
     return dw
 
 
+# ------------------------------------------------------------------------------------------------ strided dense conv (bf16 training)
+def _map4(t, name):
+    t = _dev(t, name, torch.bfloat16)
+    if t.dim() != 4:
+        raise FutureDetHipError("%s must be a [B, H, W, C] map (got %s)" % (name, tuple(t.shape)))
+    return t
+
+
+def _out_map(out, shape, like, name):
+    """``out`` checked against ``shape``, or a new bf16 tensor of that shape on ``like``'s device"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.bfloat16, device=like.device)
+    _dev(out, name, torch.bfloat16)
+    if tuple(out.shape) != tuple(shape):
+        raise FutureDetHipError("%s must be %s (got %s)" % (name, tuple(shape), tuple(out.shape)))
+    return out
+
+
+def conv2d_s2_dgrad_bf16(dy_nhwc, wpk_t, H, W, cin, out=None):
+    """Input gradient of the 3 x 3 / stride 2 / padding 1 convolution of an [B, H, W, cin] map: dy [B, (H-1)//2+1, (W-1)//2+1, Cout] bf16
+    and ``wpk_t`` = pack_conv2d_weight_device(w, transposed=True) -> dx [B, H, W, cin] bf16, every element written
+    (fd_conv2d_s2_dgrad_bf16)."""
+    L = _lib.load()
+    dy = _map4(dy_nhwc, "dy_nhwc")
+    B, Ho, Wo, cout = dy.shape
+    if H < 1 or W < 1 or (Ho, Wo) != ((H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise FutureDetHipError("conv2d_s2_dgrad_bf16: dy %s is not the stride-2 map of %d x %d" % (tuple(dy.shape), H, W))
+    _dev(wpk_t, "wpk_t", torch.uint8)
+    if wpk_t.numel() != L.fd_conv2d_packed_weight_bytes(cin, cout, 3) or wpk_t.numel() == 0:
+        raise FutureDetHipError("conv2d_s2_dgrad_bf16: wpk_t is not the transposed pack of a [%d, %d, 3, 3] weight" % (cout, cin))
+    out = _out_map(out, (B, H, W, cin), dy, "out")
+    check(L.fd_conv2d_s2_dgrad_bf16(_p(dy), B, H, W, cin, cout, _p(wpk_t), _p(out), _stream()), "fd_conv2d_s2_dgrad_bf16")
+    return out
+
+
+def conv2d_wgrad_s2_bf16(x_nhwc, dy_nhwc):
+    """Weight gradient of the 3 x 3 / stride 2 / padding 1 convolution: x [B,H,W,Cin] and dy [B,(H-1)//2+1,(W-1)//2+1,Cout] bf16 contiguous
+    -> dW [Cout, Cin, 3, 3] float32 (fd_conv2d_wgrad_s2_bf16: deterministic, no atomics)."""
+    L = _lib.load()
+    x, dy = _map4(x_nhwc, "x_nhwc"), _map4(dy_nhwc, "dy_nhwc")
+    B, H, W, cin = x.shape
+    cout = dy.shape[3]
+    if tuple(dy.shape[:3]) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise FutureDetHipError("conv2d_wgrad_s2_bf16: dy %s is not the stride-2 map of x %s" % (tuple(dy.shape), tuple(x.shape)))
+    nbytes = L.fd_conv2d_wgrad_s2_bf16_workspace_bytes(B, H, W, cin, cout)
+    if nbytes == 0:
+        raise FutureDetHipError("conv2d_wgrad_s2_bf16: unsupported problem %s -> %d channels" % (tuple(x.shape), cout))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+    check(L.fd_conv2d_wgrad_s2_bf16(_p(x), _p(dy), B, H, W, cin, cout, _p(ws), ws.numel(), _p(dw), _stream()), "fd_conv2d_wgrad_s2_bf16")
+    return dw
+
+
+PACK_UP2, PACK_DOWN2 = 0, 1
+
+
+def pack_conv2d_weight_2x2_device(w, kind, fine_major=False):
+    """The packed weights of the 2 x 2 / stride 2 pair from ``w``, fp32 [Ccoarse, Cfine, 2, 2] on the device (the layout of both
+    nn.Conv2d(2, 2) and nn.ConvTranspose2d(2, 2); ``fine_major``: [Cfine, Ccoarse, 2, 2]), in one launch (fd_conv2d_pack_weight_2x2_dev).
+    PACK_UP2: the four packs of conv2d_up2_bf16, tap 2 dy + dx = pack_conv2d_weight(w[:, :, dy, dx].t()[..., None, None]), back to back;
+    PACK_DOWN2: the pack of conv2d_down2_bf16 = pack_conv2d_weight(w.permute(0, 2, 3, 1).reshape(Ccoarse, 4 * Cfine, 1, 1))."""
+    L = _lib.load()
+    w = _dev(w.detach(), "w", torch.float32)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (2, 2) or kind not in (PACK_UP2, PACK_DOWN2):
+        raise FutureDetHipError("pack_conv2d_weight_2x2_device: need a [Ccoarse, Cfine, 2, 2] weight and kind PACK_UP2 or PACK_DOWN2 (got %s, %r)"
+                                % (tuple(w.shape), kind))
+    cc, cf = (w.shape[1], w.shape[0]) if fine_major else (w.shape[0], w.shape[1])
+    nbytes = L.fd_conv2d_packed_weight_2x2_bytes(cc, cf, kind)
+    if nbytes == 0:
+        raise FutureDetHipError("pack_conv2d_weight_2x2_device: unsupported weight shape %s for kind %d" % (tuple(w.shape), kind))
+    out = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
+    check(L.fd_conv2d_pack_weight_2x2_dev(_p(w), cc, cf, kind, int(bool(fine_major)), _p(out), _stream()), "fd_conv2d_pack_weight_2x2_dev")
+    return out
+
+
+def conv2d_up2_bf16(x_nhwc, wpk4, c_fine, out=None):
+    """"up2": coarse x [B, H, W, Ccoarse] bf16 -> fine [B, 2H, 2W, c_fine] bf16, fine[b, 2y+dy, 2x+dx] = x[b, y, x] . W(., ., dy, dx) -- four
+    1 x 1 launches of fd_conv2d_nhwc_bf16 with pixel placement on the four packs of PACK_UP2."""
+    x = _map4(x_nhwc, "x_nhwc")
+    B, H, W, cc = x.shape
+    _dev(wpk4, "wpk4", torch.uint8)
+    per = _lib.load().fd_conv2d_packed_weight_bytes(c_fine, cc, 1)
+    if per == 0 or wpk4.numel() != 4 * per:
+        raise FutureDetHipError("conv2d_up2_bf16: wpk4 is not the PACK_UP2 pack of a [%d, %d, 2, 2] weight" % (cc, c_fine))
+    out = _out_map(out, (B, 2 * H, 2 * W, c_fine), x, "out")
+    for tap in range(4):
+        conv2d_nhwc_bf16(x, wpk4[tap * per:(tap + 1) * per], None, c_fine, 1, stride=1, relu=False, out=out, osy=2, osx=2, ooy=tap >> 1, oox=tap & 1)
+    return out
+
+
+def conv2d_down2_bf16(x_nhwc, wpk, c_coarse, out=None):
+    """"down2": fine x [B, H, W, Cfine] bf16 -> coarse [B, H//2, W//2, c_coarse] bf16, the sum over the 2 x 2 block of x . W(., ., dy, dx), on
+    the PACK_DOWN2 pack (fd_conv2d_down2_bf16).  The trailing row or column of an odd H or W is not read."""
+    L = _lib.load()
+    x = _map4(x_nhwc, "x_nhwc")
+    B, H, W, cf = x.shape
+    _dev(wpk, "wpk", torch.uint8)
+    if wpk.numel() != L.fd_conv2d_packed_weight_2x2_bytes(c_coarse, cf, PACK_DOWN2) or wpk.numel() == 0:
+        raise FutureDetHipError("conv2d_down2_bf16: wpk is not the PACK_DOWN2 pack of a [%d, %d, 2, 2] weight" % (c_coarse, cf))
+    out = _out_map(out, (B, H // 2, W // 2, c_coarse), x, "out")
+    check(L.fd_conv2d_down2_bf16(_p(x), B, H, W, cf, _p(wpk), c_coarse, _p(out), _stream()), "fd_conv2d_down2_bf16")
+    return out
+
+
+def conv2d_wgrad_2x2_bf16(coarse_nhwc, fine_nhwc, fine_major=False):
+    """Weight gradient of the 2 x 2 / stride 2 pair: coarse [B, H//2, W//2, Ccoarse] and fine [B, H, W, Cfine] bf16 contiguous -> dW float32
+    [Ccoarse, Cfine, 2, 2] (``fine_major``: [Cfine, Ccoarse, 2, 2]), dW(a, f, dy, dx) = the sum over coarse pixels of
+    coarse[b, y, x, a] fine[b, 2y+dy, 2x+dx, f] (fd_conv2d_wgrad_2x2_bf16: deterministic, no atomics)."""
+    L = _lib.load()
+    co, fi = _map4(coarse_nhwc, "coarse_nhwc"), _map4(fine_nhwc, "fine_nhwc")
+    B, H, W, cf = fi.shape
+    cc = co.shape[3]
+    if tuple(co.shape[:3]) != (B, H // 2, W // 2):
+        raise FutureDetHipError("conv2d_wgrad_2x2_bf16: coarse %s is not the 2 x 2 / stride 2 map of fine %s" % (tuple(co.shape), tuple(fi.shape)))
+    nbytes = L.fd_conv2d_wgrad_2x2_bf16_workspace_bytes(B, H, W, cc, cf)
+    if nbytes == 0:
+        raise FutureDetHipError("conv2d_wgrad_2x2_bf16: unsupported problem %s, %s" % (tuple(co.shape), tuple(fi.shape)))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=fi.device)
+    dw = torch.empty((cf, cc, 2, 2) if fine_major else (cc, cf, 2, 2), dtype=torch.float32, device=fi.device)
+    check(L.fd_conv2d_wgrad_2x2_bf16(_p(co), _p(fi), B, H, W, cc, cf, int(bool(fine_major)), _p(ws), ws.numel(), _p(dw), _stream()),
+          "fd_conv2d_wgrad_2x2_bf16")
+    return dw
+
+
 # ------------------------------------------------------------------------------------------------ head tail (bf16 training)
 def head_tail_max_groups():
     """Group records one launch of the head-tail kernels takes; the wrappers below split longer lists."""

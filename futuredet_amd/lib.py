@@ -175,6 +175,14 @@ SIGNATURES = {
     "fd_conv2d_wgrad_bf16_chunk": (c_int, []),
     "fd_conv2d_wgrad_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fd_conv2d_wgrad_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fd_conv2d_s2_dgrad_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "fd_conv2d_wgrad_s2_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fd_conv2d_wgrad_s2_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "fd_conv2d_down2_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "fd_conv2d_packed_weight_2x2_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fd_conv2d_pack_weight_2x2_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "fd_conv2d_wgrad_2x2_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fd_conv2d_wgrad_2x2_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "fd_head_tail_bf16_max_groups": (c_int, []),
     "fd_head_tail_wgrad_bf16_chunk": (c_int, []),
     "fd_head_tail_wgrad_bf16_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

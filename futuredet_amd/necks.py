@@ -104,8 +104,12 @@ class RPN(nn.Module):
     def forward_mixed(self, x):
         """Training-mode forward in mixed precision (train_dtype = torch.bfloat16, device maps): the BEV map is converted once to bf16
         channels-last, every block and deblock runs through dense_train.run_stack_bf16 -- the stride-1 3 x 3 convolutions and the
-        1 x 1 deblock on fd_conv2d_nhwc_bf16 / fd_conv2d_wgrad_bf16 with fp32 master weights and fp32 weight gradients, BatchNorm with fp32
-        statistics -- and the concatenated map is returned fp32 and NCHW-contiguous, which is what the head sees from forward_modules.
+        1 x 1 deblock on fd_conv2d_nhwc_bf16 / fd_conv2d_wgrad_bf16 with fp32 master weights and fp32 weight gradients, the 3 x 3 /
+        stride 2 convolution that opens a down-sampling stage on dense_train.conv2d_s2_bf16 and the ConvTranspose2d(2, stride 2) deblock
+        on dense_train.conv_transpose2d_k2_bf16 (fd_conv2d_strided_grad_bf16.hip), BatchNorm with fp32 statistics -- and the concatenated
+        map is returned fp32 and NCHW-contiguous, which is what the head sees from forward_modules.  Any other convolution (a bias, other
+        kernel sizes or strides; also the Conv2d(2, stride 2) deblock of the PointPillars neck, which was measured no faster on
+        dense_train.conv2d_k2s2_bf16) runs its module on an fp32 copy of its input.
         BatchNorm2d runs the backbone's un-fused recipe, bn(x.float()) + ReLU + one rounding; with ``fused_bn`` every module that
         dense_bn.batch_norm2d_nhwc_fusable accepts (training mode, a multiple of 32 channels up to 512) runs with its ReLU on
         fd_dense_bn_nhwc.hip instead (dense_bn.batch_norm2d_act_nhwc: bf16 channels-last in and out, fp32 statistics, no fp32 copy of the

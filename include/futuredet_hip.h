@@ -932,6 +932,52 @@ int fd_dense_bn_nhwc_train_backward_bf16(const uint16_t *dy, const uint16_t *x, 
                                          const fd_dense_bn_nhwc_group *groups, int n_groups, int64_t n, int C, int relu, uint16_t *dx,
                                          float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Mixed-precision training of the dense convolutions that change resolution (fd_conv2d_strided_grad_bf16.hip; the weight gradients
+ * are instantiations of fd_conv2d_wgrad_bf16's kernel in fd_conv2d_grad_bf16.hip).  Purely additive: fd_abi_version() stays 8.
+ * They replace the fp32 torch convolutions, forward and backward, of det3d/models/necks/rpn.py:124-128 (ZeroPad2d(1) + Conv2d(3,
+ * stride 2): the opener of a down-sampling stage), rpn.py:82-86 (the ConvTranspose2d(k = stride = 2) deblock) and rpn.py:96-102 (the
+ * Conv2d(k = stride = 2) deblock of us_layer_strides 0.5).  All maps are bf16 NHWC, all channel counts multiples of 32, sums are fp32
+ * on the matrix core, a bf16 result is rounded once (to nearest even); no atomics, no allocation, no synchronisation.
+ *
+ * 3 x 3 / stride 2 / padding 1, x [B,H,W,cin] -> y [B,Ho,Wo,cout], Ho = (H - 1) / 2 + 1 (H and W even or odd).  The forward is
+ * fd_conv2d_nhwc_bf16 with stride 2.
+ *   fd_conv2d_s2_dgrad_bf16: dx[b,iy,ix,ci] = sum over (ky, kx, co) of dy[b,(iy+1-ky)/2,(ix+1-kx)/2,co] w[co][ci][ky][kx] over the taps
+ *                     whose quotients are integers inside Ho x Wo.  wpacked_t: the mode-1 pack of fd_conv2d_pack_weight_dev (ks 3).
+ *                     Every element of dx is written.
+ *   fd_conv2d_wgrad_s2_bf16: dw[co][ci][ky][kx] = sum over (b, oy, ox) of dy[b,oy,ox,co] x[b,2oy+ky-1,2ox+kx-1,ci] (in-image terms), fp32,
+ *                     overwritten.  fd_conv2d_wgrad_bf16's design over the pixels of dy: chunks of fd_conv2d_wgrad_bf16_chunk(), one
+ *                     fp32 partial per (chunk, tap) in `workspace` (fd_conv2d_wgrad_s2_bf16_workspace_bytes; 0 = bad arguments), summed in
+ *                     chunk order: the same bits on every run; the workspace need not be initialised.
+ *
+ * The 2 x 2 / stride 2 pair between a fine map [B,H,W,c_fine] and a coarse map [B,H/2,W/2,c_coarse] (the trailing row or column of an
+ * odd H or W is not read), with W(a, f, dy, dx) the parameter at coarse-side channel a and fine-side channel f -- both nn.Conv2d(2, 2)
+ * ([cout = coarse][cin = fine][2][2]) and nn.ConvTranspose2d(2, 2) ([cin = coarse][cout = fine][2][2]) store [c_coarse][c_fine][2][2];
+ * fine_major = 1 reads or writes the other order, [c_fine][c_coarse][2][2]:
+ *   "up2":   fine[b,2y+dy,2x+dx,f] = sum over a of coarse[b,y,x,a] W(a,f,dy,dx) -- the forward of ConvTranspose2d(2, 2), the input
+ *            gradient of Conv2d(2, 2): four fd_conv2d_nhwc_bf16 launches (ks 1, osy = osx = 2, ooy = dy, oox = dx), tap 2 dy + dx with
+ *            the pack at offset (2 dy + dx) fd_conv2d_packed_weight_bytes(c_fine, c_coarse, 1) of the kind-0 pack below.
+ *   fd_conv2d_down2_bf16: "down2", coarse[b,y,x,a] = sum over (dy, dx, f) of fine[b,2y+dy,2x+dx,f] W(a,f,dy,dx) -- the forward of
+ *            Conv2d(2, 2), the input gradient of ConvTranspose2d(2, 2); wpacked: the kind-1 pack below.
+ *   fd_conv2d_pack_weight_2x2_dev: w fp32 DEVICE memory -> kind 0: the four up2 packs, back to back, each byte for byte
+ *            fd_conv2d_pack_weight of the [c_fine][c_coarse][1][1] weight W(., ., dy, dx) transposed (c_coarse % 32 == 0, c_fine padded
+ *            to 32); kind 1: fd_conv2d_pack_weight of the [c_coarse][4 c_fine][1][1] weight with input channel (2 dy + dx) c_fine + f
+ *            (c_fine % 32 == 0, c_coarse padded to 32).  fd_conv2d_packed_weight_2x2_bytes: the size (0 = bad arguments).  One launch.
+ *   fd_conv2d_wgrad_2x2_bf16: dw(a,f,dy,dx) = sum over coarse pixels of coarse[b,y,x,a] fine[b,2y+dy,2x+dx,f], fp32, overwritten, in
+ *            the layout fine_major selects; chunks of coarse pixels, partials and reduction as above
+ *            (fd_conv2d_wgrad_2x2_bf16_workspace_bytes; H and W are the fine map's).
+ * ------------------------------------------------------------------------------------------------- */
+int fd_conv2d_s2_dgrad_bf16(const void *dy, int B, int H, int W, int cin, int cout, const void *wpacked_t, void *dx, fd_stream_t stream);
+size_t fd_conv2d_wgrad_s2_bf16_workspace_bytes(int B, int H, int W, int cin, int cout);
+int fd_conv2d_wgrad_s2_bf16(const void *x, const void *dy, int B, int H, int W, int cin, int cout, void *workspace, size_t workspace_bytes,
+                            float *dw, fd_stream_t stream);
+int fd_conv2d_down2_bf16(const void *x, int B, int H, int W, int c_fine, const void *wpacked, int c_coarse, void *y, fd_stream_t stream);
+size_t fd_conv2d_packed_weight_2x2_bytes(int c_coarse, int c_fine, int kind);
+int fd_conv2d_pack_weight_2x2_dev(const float *w, int c_coarse, int c_fine, int kind, int fine_major, void *wpacked, fd_stream_t stream);
+size_t fd_conv2d_wgrad_2x2_bf16_workspace_bytes(int B, int H, int W, int c_coarse, int c_fine);
+int fd_conv2d_wgrad_2x2_bf16(const void *coarse, const void *fine, int B, int H, int W, int c_coarse, int c_fine, int fine_major,
+                             void *workspace, size_t workspace_bytes, float *dw, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
