@@ -350,6 +350,39 @@ class PointPillarsScatter(nn.Module):
                                       channels_last=self.dense_channels_last)
 
 
+    def forward_static(self, voxel_features, coords, counts, batch_size, input_shape):
+        """The scatter of a fixed-capacity batch: voxel_features [B * cap, C] and coords [B * cap, 4] hold sample b's pillars in the first
+        counts[b] (device int32[B]) rows of segment b; the rows behind are not read, and their gradient is 0.  No host read."""
+        self.nx = int(input_shape[0])
+        self.ny = int(input_shape[1])
+        return _ScatterSegFn.apply(voxel_features, coords.int().contiguous(), counts, batch_size, self.ny, self.nx, self.dense_channels_last)
+
+
+class _ScatterSegFn(torch.autograd.Function):
+    """_ScatterFn for B segments with device counts: one fd_pillar_scatter / fd_dense_gather per segment, each with its count pointer."""
+
+    @staticmethod
+    def forward(ctx, feats, coords, counts, batch_size, ny, nx, channels_last):
+        B = counts.shape[0]
+        cap = feats.shape[0] // B
+        ctx.coords, ctx.counts, ctx.cap = coords, counts, cap
+        canvas = None
+        for b in range(B):
+            sl = slice(b * cap, (b + 1) * cap)
+            canvas = hip_ops.pillar_scatter(feats[sl], coords[sl], counts[b:b + 1], batch_size, ny, nx, channels_last=channels_last,
+                                            out=canvas, zero_first=(b == 0))
+        return canvas
+
+    @staticmethod
+    def backward(ctx, dcanvas):
+        coords, counts, cap = ctx.coords, ctx.counts, ctx.cap
+        dcanvas = dcanvas.float()
+        d = torch.cat([hip_ops.pillar_scatter_backward(dcanvas, coords[b * cap:(b + 1) * cap], n_dev=counts[b:b + 1])
+                       for b in range(counts.shape[0])])
+        ctx.coords = ctx.counts = None
+        return d, None, None, None, None, None, None
+
+
 class _ScatterFn(torch.autograd.Function):
     """PointPillarsScatter with its backward: d(pillar row) = dcanvas[b, :, y, x] (fd_dense_gather with D = 1, any canvas strides)."""
 

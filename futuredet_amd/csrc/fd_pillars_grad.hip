@@ -25,6 +25,13 @@
 // Determinism: block b owns pillars [b * ppb, (b + 1) * ppb) with ppb a function of M only; wave w of the block takes the
 // block's pillars w, w + 4, ...; waves are added in wave order; partials are reduced over blocks in 16 fixed slices whose sums
 // are added in slice order.  No atomics: two runs give the same bits.
+//
+// Counts.  The batch is n_seg <= 16 segments of seg_stride rows; segment b's live pillars are its first cnt_b rows.  The logical
+// batch is their concatenation in segment order, M = sum cnt_b pillars: every kernel derives M, ppb and the number of live blocks
+// from the counts itself and maps logical pillar p to its physical row through the counts' prefix, so the summation order is that
+// of M contiguous pillars.  The counts come from the host (fd_pillar_train_forward: one segment of m rows) or from device memory
+// (fd_pillar_train_forward_dev: launched for the capacity; blocks behind the last live one leave at once, rows behind a count are
+// never read, their `out` rows are written as 0, and a batch of N < 2 rows gives zeros everywhere).
 #include "fd_common.h"
 
 namespace {
@@ -46,23 +53,65 @@ constexpr int D_SUM1 = 0, D_CM1 = D_SUM1 + kFin, D_SUM2 = D_CM1 + kFin * kFin, D
 constexpr int F_MU1 = 0, F_IS1 = F_MU1 + kU1, F_MU2 = F_IS1 + kU1, F_IS2 = F_MU2 + kU2, F_A = F_IS2 + kU2, F_C0 = F_A + kU2 * kU2,
               F_K2 = F_C0 + kU2, F_END = F_K2 + kU2;
 
-inline int pillars_per_block(int64_t m) {
-    int64_t ppb = (m + kMaxBlocks - 1) / kMaxBlocks;
+__host__ __device__ inline int pillars_per_block(long long m) {
+    long long ppb = (m + kMaxBlocks - 1) / kMaxBlocks;
     if (ppb < 16) ppb = 16;
     return (int)((ppb + kWaves - 1) / kWaves * kWaves);
 }
 
+constexpr int kMaxSegs = 16;
+
+// Where the pillars are.  counts == nullptr: one segment of host_m rows (the host-count entries).
+struct Segs {
+    const int *counts;  // device int32[n_seg], or nullptr
+    long long stride;   // rows per segment
+    long long host_m;
+    int n_seg;
+};
+
+struct Batch {
+    long long m;  // live pillars
+    int ppb, nb;  // pillars per block, live blocks (0 for the empty batch, N < 2)
+};
+
+__device__ __forceinline__ long long seg_count(const Segs &s, int b) {
+    if (!s.counts) return s.host_m;
+    const long long c = s.counts[b];
+    return c < 0 ? 0 : (c > s.stride ? s.stride : c);
+}
+
+__device__ __forceinline__ Batch resolve(const Segs &s, int P) {
+    Batch B;
+    B.m = 0;
+    for (int b = 0; b < s.n_seg; ++b) B.m += seg_count(s, b);
+    B.ppb = pillars_per_block(B.m);
+    B.nb = B.m * P > 1 ? (int)((B.m + B.ppb - 1) / B.ppb) : 0;
+    return B;
+}
+
+// physical row of logical pillar p < M
+__device__ __forceinline__ long long phys_row(const Segs &s, long long p) {
+    int b = 0;
+    for (; b < s.n_seg - 1; ++b) {
+        const long long c = seg_count(s, b);
+        if (p < c) break;
+        p -= c;
+    }
+    return (long long)b * s.stride + p;
+}
+
 struct Layout {
-    int ppb, nb;
+    int grid;  // blocks launched: the largest number of live blocks any count <= cap can give
     size_t part, arg2, xsel, d64, f32, total;
 };
 
+// cap = rows of the buffers (m of the host-count entries, n_seg * seg_stride of the device-count ones)
 Layout layout(int64_t m) {
     Layout L;
-    L.ppb = pillars_per_block(m);
-    L.nb = (int)((m + L.ppb - 1) / L.ppb);
+    const int64_t g = (m + 15) / 16;  // ppb >= 16
+    L.grid = (int)(g < kMaxBlocks ? (g < 1 ? 1 : g) : kMaxBlocks);
     size_t o = 0;
-    L.part = o; o += fd::align_up((size_t)L.nb * kPartStride * sizeof(float), 256);
+    L.part = o; o += fd::align_up((size_t)L.grid * kPartStride * sizeof(float), 256);
     L.arg2 = o; o += fd::align_up((size_t)m * kU2, 256);
     L.xsel = o; o += fd::align_up((size_t)m * kU2 * sizeof(float), 256);
     L.d64 = o;  o += fd::align_up((size_t)D_END * sizeof(double), 256);
@@ -75,8 +124,8 @@ struct TrainArgs {
     const float *voxels;
     const int *num_points;
     const int *coors;  // [M,4] (b,z,y,x)
-    long long m;
-    int P, ndim, fin, with_distance, ppb;
+    Segs seg;
+    int P, ndim, fin, with_distance;
     float vx, vy, x_off, y_off;
     const float *w1, *g1, *b1, *w2, *g2, *b2;
     const float *st;  // fp32 workspace slots
@@ -90,7 +139,7 @@ struct WaveLds {
     __attribute__((aligned(16))) float x[kMaxP][kU2];  // in2 rows: [a1 (32), max1 (32)]; rows >= P are 0
 };
 
-// Decorated, masked features of pillar m into w.f (pillar_encoder.py:113-149; rows >= P and dead pillars are 0).  Block-uniform.
+// Decorated, masked features of the pillar in physical row m into w.f (pillar_encoder.py:113-149; rows >= P and dead pillars are 0).  Block-uniform.
 __device__ void decorate(const TrainArgs &a, long long m, bool live, WaveLds &w, int lane) {
     const int P = a.P, nd = a.ndim;
     if (live)
@@ -180,11 +229,13 @@ __global__ void __launch_bounds__(kWaves * 64) stats_pass(TrainArgs a) {
     __shared__ float s_sum[kWaves][D];
     __shared__ float s_mean[D];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long p0 = (long long)blockIdx.x * a.ppb, p1 = min(p0 + a.ppb, a.m);
+    const Batch B = resolve(a.seg, a.P);
+    if ((int)blockIdx.x >= B.nb) return;  // block-uniform, before any barrier
+    const long long p0 = (long long)blockIdx.x * B.ppb, p1 = min(p0 + B.ppb, B.m);
     WaveLds &w = s_w[wave];
     Layer1Params l1;
     if (LAYER == 2) load_layer1(a, lane & 31, l1);
-    const int iters = a.ppb / kWaves;
+    const int iters = B.ppb / kWaves;
     float colsum = 0.f;  // lane c < D: the wave's column sum
     for (int pass = 0; pass < 2; ++pass) {
         f32x4 acc[NT][NT];
@@ -193,9 +244,9 @@ __global__ void __launch_bounds__(kWaves * 64) stats_pass(TrainArgs a) {
 #pragma unroll
             for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int it = 0; it < iters; ++it) {
-            const long long m = p0 + wave + (long long)kWaves * it;
-            const bool live = m < p1;
-            decorate(a, m, live, w, lane);
+            const long long lp = p0 + wave + (long long)kWaves * it;
+            const bool live = lp < p1;
+            decorate(a, live ? phys_row(a.seg, lp) : 0, live, w, lane);
             if (LAYER == 2) {
                 float mx;
                 int arg;
@@ -271,9 +322,12 @@ __global__ void __launch_bounds__(kWaves * 64) stats_pass(TrainArgs a) {
 // out[e] = sum over the blocks' partials, in double precision: slice s of 16 sums blocks [s * per, (s + 1) * per) in order, the
 // slices are added in slice order.  mode 0: part[off + e];  1: n_b * mean_b[e];  2: M2_b[e] + n_b (mean_b[i] - mu_i)(mean_b[j] - mu_j),
 // e = i * D + j, mu = msum / n_tot (Chan).
-__global__ void __launch_bounds__(256) reduce_parts(const float *__restrict__ part, int nb, int off, int cnt, int mode, int D,
-                                                    const double *__restrict__ msum, double n_tot, double *__restrict__ out) {
+__global__ void __launch_bounds__(256) reduce_parts(const float *__restrict__ part, Segs seg, int P, int off, int cnt, int mode, int D,
+                                                    const double *__restrict__ msum, double *__restrict__ out) {
     __shared__ double s_acc[256];
+    const Batch B = resolve(seg, P);
+    const int nb = B.nb;  // (0 for the empty batch: every sum is 0)
+    const double n_tot = (double)B.m * P;
     const int el = threadIdx.x & 15, s = threadIdx.x >> 4;
     const int e = blockIdx.x * 16 + el;
     const int per = (nb + kSlices - 1) / kSlices;
@@ -309,8 +363,15 @@ __global__ void __launch_bounds__(256) reduce_parts(const float *__restrict__ pa
 // Batch statistics of a layer from its input statistics: mean = W mean_in, var = diag(W C W^T) / N; WC = W C kept for the backward.
 template <int U, int D>
 __global__ void __launch_bounds__(256) finish_stats(const float *__restrict__ wt, int win, const double *__restrict__ sum, const double *__restrict__ cm,
-                                                    double n_tot, float eps, double *__restrict__ wc, float *__restrict__ mean_out,
+                                                    Segs seg, int P, float eps, double *__restrict__ wc, float *__restrict__ mean_out,
                                                     float *__restrict__ var_out, float *__restrict__ mu_ws, float *__restrict__ is_ws) {
+    const Batch B = resolve(seg, P);
+    const double n_tot = (double)B.m * P;
+    if (B.nb == 0) {  // the empty batch: no statistics
+        for (int t = threadIdx.x; t < U * D; t += 256) wc[t] = 0.0;
+        if (threadIdx.x < U) mean_out[threadIdx.x] = var_out[threadIdx.x] = mu_ws[threadIdx.x] = is_ws[threadIdx.x] = 0.f;
+        return;
+    }
     for (int t = threadIdx.x; t < U * D; t += 256) {
         const int u = t / D, c = t - u * D;
         double s = 0.0;
@@ -339,7 +400,17 @@ __global__ void __launch_bounds__(kWaves * 64) output_pass(TrainArgs a, float *_
                                                             float *__restrict__ xsel) {
     __shared__ WaveLds s_w[kWaves];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long p0 = (long long)blockIdx.x * a.ppb, p1 = min(p0 + a.ppb, a.m);
+    const Batch B = resolve(a.seg, a.P);
+    if (a.seg.counts) {  // device counts: the rows behind a count (every row of the empty batch) are 0
+        const long long cells = (long long)a.seg.n_seg * a.seg.stride * kU2;
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (long long)gridDim.x * blockDim.x) {
+            const long long row = i / kU2;
+            const int b = (int)(row / a.seg.stride);
+            if (B.nb == 0 || row - (long long)b * a.seg.stride >= seg_count(a.seg, b)) out[i] = 0.f;
+        }
+    }
+    if ((int)blockIdx.x >= B.nb) return;  // block-uniform, before any barrier
+    const long long p0 = (long long)blockIdx.x * B.ppb, p1 = min(p0 + B.ppb, B.m);
     WaveLds &w = s_w[wave];
     Layer1Params l1;
     load_layer1(a, lane & 31, l1);
@@ -347,10 +418,11 @@ __global__ void __launch_bounds__(kWaves * 64) output_pass(TrainArgs a, float *_
 #pragma unroll
     for (int c = 0; c < 2 * kU1; ++c) w2[c] = a.w2[lane * 2 * kU1 + c];
     const float mu2 = a.st[F_MU2 + lane], is2 = a.st[F_IS2 + lane], sc2 = a.g2[lane] * is2, b2 = a.b2[lane];
-    const int iters = a.ppb / kWaves;
+    const int iters = B.ppb / kWaves;
     for (int it = 0; it < iters; ++it) {
-        const long long m = p0 + wave + (long long)kWaves * it;
-        const bool live = m < p1;
+        const long long lp = p0 + wave + (long long)kWaves * it;
+        const bool live = lp < p1;
+        const long long m = live ? phys_row(a.seg, lp) : 0;
         decorate(a, m, live, w, lane);
         float mx1;
         int arg1;
@@ -393,14 +465,17 @@ __global__ void __launch_bounds__(kWaves * 64) output_pass(TrainArgs a, float *_
 }
 
 // ---- backward 1: per-block sums of g2 = dout where the output is > 0, and of g2 x^2(arg row).  Partial [dbeta2[64], dgamma2[64]].
-__global__ void __launch_bounds__(kWaves * 64) sparse_pass(long long m_tot, int ppb, const float *__restrict__ dout,
+__global__ void __launch_bounds__(kWaves * 64) sparse_pass(Segs seg, int P, const float *__restrict__ dout,
                                                             const unsigned char *__restrict__ arg2, const float *__restrict__ xsel,
                                                             float *__restrict__ part) {
     __shared__ float s_red[kWaves][2 * kU2];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long p0 = (long long)blockIdx.x * ppb, p1 = min(p0 + ppb, m_tot);
+    const Batch B = resolve(seg, P);
+    if ((int)blockIdx.x >= B.nb) return;  // block-uniform, before any barrier
+    const long long p0 = (long long)blockIdx.x * B.ppb, p1 = min(p0 + B.ppb, B.m);
     float sb = 0.f, sg = 0.f;
-    for (long long m = p0 + wave; m < p1; m += kWaves) {
+    for (long long lp = p0 + wave; lp < p1; lp += kWaves) {
+        const long long m = phys_row(seg, lp);
         if (arg2[m * kU2 + lane] & 0x80) {
             const float g = dout[m * kU2 + lane];
             sb += g;
@@ -419,8 +494,14 @@ __global__ void __launch_bounds__(kWaves * 64) sparse_pass(long long m_tot, int 
 
 // dbeta2 / dgamma2 out; the dense BN-backward terms of layer 2 as A (64 x 64), c0 (64) and k2 = gamma2 invstd2.
 __global__ void __launch_bounds__(256) finish_sparse(const float *__restrict__ w2, const float *__restrict__ g2, const double *__restrict__ bs,
-                                                     double n_tot, float *__restrict__ st, float *__restrict__ dgamma2, float *__restrict__ dbeta2) {
+                                                     Segs seg, int P, float *__restrict__ st, float *__restrict__ dgamma2, float *__restrict__ dbeta2) {
     __shared__ double s_a[kU2], s_b[kU2];
+    const Batch B = resolve(seg, P);
+    const double n_tot = (double)B.m * P;
+    if (B.nb == 0) {  // the empty batch: no gradient (the rows pass has no live block and reads none of st)
+        if (threadIdx.x < kU2) dbeta2[threadIdx.x] = dgamma2[threadIdx.x] = 0.f;
+        return;
+    }
     if (threadIdx.x < kU2) {
         const int v = threadIdx.x;
         const double is2 = st[F_IS2 + v], mu2 = st[F_MU2 + v];
@@ -454,7 +535,9 @@ __global__ void __launch_bounds__(kWaves * 64) rows_pass(TrainArgs a, const floa
     __shared__ int s_arg[kWaves][kU2];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int u = lane & 31, g = lane >> 5;
-    const long long p0 = (long long)blockIdx.x * a.ppb, p1 = min(p0 + a.ppb, a.m);
+    const Batch B = resolve(a.seg, a.P);
+    if ((int)blockIdx.x >= B.nb) return;  // block-uniform, before any barrier
+    const long long p0 = (long long)blockIdx.x * B.ppb, p1 = min(p0 + B.ppb, B.m);
     WaveLds &w = s_w[wave];
     const float *A = a.st + F_A;
     const float *c0 = a.st + F_C0;
@@ -471,10 +554,11 @@ __global__ void __launch_bounds__(kWaves * 64) rows_pass(TrainArgs a, const floa
     for (int v = 0; v < kU2; ++v) sp[v] = 0.f;
     float sdy = 0.f, sdyx = 0.f;
     const int P = a.P;
-    const int iters = a.ppb / kWaves;
+    const int iters = B.ppb / kWaves;
     for (int it = 0; it < iters; ++it) {
-        const long long m = p0 + wave + (long long)kWaves * it;
-        const bool live = m < p1;
+        const long long lp = p0 + wave + (long long)kWaves * it;
+        const bool live = lp < p1;
+        const long long m = live ? phys_row(a.seg, lp) : 0;
         decorate(a, m, live, w, lane);
         float mx1;
         int arg1;
@@ -588,8 +672,16 @@ __global__ void __launch_bounds__(kWaves * 64) rows_pass(TrainArgs a, const floa
 
 // dbeta1, dgamma1, dW1 [32, fin], dW2 [64, 64] from the reduced row-pass sums and the forward's statistics.
 __global__ void __launch_bounds__(256) finish_rows(const float *__restrict__ g1, const float *__restrict__ g2, int fin, const double *__restrict__ d64,
-                                                   const float *__restrict__ st, double n_tot, float *__restrict__ dw1, float *__restrict__ dgamma1,
+                                                   const float *__restrict__ st, Segs seg, int P, float *__restrict__ dw1, float *__restrict__ dgamma1,
                                                    float *__restrict__ dbeta1, float *__restrict__ dw2) {
+    const Batch B = resolve(seg, P);
+    const double n_tot = (double)B.m * P;
+    if (B.nb == 0) {  // the empty batch: no gradient
+        if (threadIdx.x < kU1) dbeta1[threadIdx.x] = dgamma1[threadIdx.x] = 0.f;
+        for (int t = threadIdx.x; t < kU1 * fin; t += 256) dw1[t] = 0.f;
+        for (int t = threadIdx.x; t < kU2 * kU2; t += 256) dw2[t] = 0.f;
+        return;
+    }
     const double *br = d64 + D_BR;
     const double *bs = d64 + D_BS;
     constexpr int kSpOff = 2 * kU1 + kU1 * kFin;
@@ -611,8 +703,23 @@ __global__ void __launch_bounds__(256) finish_rows(const float *__restrict__ g1,
     }
 }
 
-void reduce(const float *part, int nb, int off, int cnt, int mode, int D, const double *msum, double n_tot, double *out, hipStream_t st) {
-    hipLaunchKernelGGL(reduce_parts, dim3((unsigned)((cnt + 15) / 16)), dim3(256), 0, st, part, nb, off, cnt, mode, D, msum, n_tot, out);
+void reduce(const float *part, const Segs &seg, int P, int off, int cnt, int mode, int D, const double *msum, double *out, hipStream_t st) {
+    hipLaunchKernelGGL(reduce_parts, dim3((unsigned)((cnt + 15) / 16)), dim3(256), 0, st, part, seg, P, off, cnt, mode, D, msum, out);
+}
+
+// The running statistics of one BatchNorm1d by torch's rule, n = P * sum cnt_b read here: num_batches_tracked += 1,
+// running_mean <- (1 - f) running_mean + f mean, running_var <- (1 - f) running_var + f var n / (n - 1), in double precision and
+// rounded once.  n < 2 (the empty batch): nothing.
+__global__ void __launch_bounds__(64) running_stats(Segs seg, int P, const float *__restrict__ mean, const float *__restrict__ var, int c,
+                                                    double f, float *__restrict__ rmean, float *__restrict__ rvar, long long *__restrict__ nbt) {
+    const Batch B = resolve(seg, P);
+    if (B.nb == 0) return;
+    const double n = (double)B.m * P, unbias = n / (n - 1.0);
+    for (int u = threadIdx.x; u < c; u += 64) {
+        rmean[u] = (float)((1.0 - f) * (double)rmean[u] + f * (double)mean[u]);
+        rvar[u] = (float)((1.0 - f) * (double)rvar[u] + f * unbias * (double)var[u]);
+    }
+    if (nbt && threadIdx.x == 0) *nbt += 1;
 }
 
 }  // namespace
@@ -622,31 +729,42 @@ extern "C" size_t fd_pillar_train_workspace_bytes(int64_t m, int max_points) {
     return layout(m).total;
 }
 
-#define FD_PT_CHECK(fn)                                                                                                                  \
+#define FD_PT_CHECK_COMMON(fn)                                                                                                           \
     FD_REQUIRE(voxels && num_points && coors4 && w1 && gamma1 && beta1 && w2 && gamma2 && beta2, fn ": null argument");                   \
     FD_REQUIRE(max_points >= 1 && max_points <= kMaxP, fn ": max_points must be in [1,%d] (got %d)", kMaxP, max_points);                  \
     FD_REQUIRE(ndim >= 3 && ndim <= 8 && ndim + 5 + (with_distance ? 1 : 0) <= kFin, fn ": ndim must be in [3,8] (got %d)", ndim);        \
     FD_REQUIRE(units1 == kU1 && units2 == kU2,                                                                                           \
                fn ": unsupported units %d -> %d: training supports the shipped stack, two PFN layers of 32 (+32 max) -> 64 units", units1, \
-               units2);                                                                                                                  \
+               units2)
+
+#define FD_PT_CHECK(fn)                                                                                                                  \
+    FD_PT_CHECK_COMMON(fn);                                                                                                              \
     FD_REQUIRE(m >= 0 && m < (1ll << 30), fn ": m out of range");                                                                         \
     FD_REQUIRE(m * max_points > 1, fn ": expected more than 1 value per channel (N = m * max_points = %lld)", (long long)(m * max_points)); \
     FD_REQUIRE(workspace && workspace_bytes >= fd_pillar_train_workspace_bytes(m, max_points), fn ": workspace too small (%zu < %zu bytes)",  \
                workspace_bytes, fd_pillar_train_workspace_bytes(m, max_points))
 
-static TrainArgs make_args(const float *voxels, const int32_t *num_points, const int32_t *coors4, int64_t m, int max_points, int ndim,
+#define FD_PT_CHECK_DEV(fn)                                                                                                              \
+    FD_PT_CHECK_COMMON(fn);                                                                                                              \
+    FD_REQUIRE(seg_counts, fn ": null seg_counts");                                                                                      \
+    FD_REQUIRE(n_seg >= 1 && n_seg <= kMaxSegs, fn ": n_seg must be in [1,%d] (got %d)", kMaxSegs, n_seg);                                \
+    FD_REQUIRE(seg_stride >= 1 && seg_stride < (1ll << 30) / n_seg, fn ": seg_stride out of range");                                      \
+    FD_REQUIRE(workspace && workspace_bytes >= fd_pillar_train_workspace_bytes((int64_t)n_seg * seg_stride, max_points),                  \
+               fn ": workspace too small (%zu < %zu bytes)", workspace_bytes,                                                             \
+               fd_pillar_train_workspace_bytes((int64_t)n_seg * seg_stride, max_points))
+
+static TrainArgs make_args(const float *voxels, const int32_t *num_points, const int32_t *coors4, const Segs &seg, int max_points, int ndim,
                            int with_distance, float vx, float vy, float x_offset, float y_offset, const float *w1, const float *gamma1,
                            const float *beta1, const float *w2, const float *gamma2, const float *beta2, const Layout &L, char *ws) {
     TrainArgs a;
     a.voxels = voxels;
     a.num_points = num_points;
     a.coors = coors4;
-    a.m = m;
+    a.seg = seg;
     a.P = max_points;
     a.ndim = ndim;
     a.fin = ndim + 5 + (with_distance ? 1 : 0);
     a.with_distance = with_distance ? 1 : 0;
-    a.ppb = L.ppb;
     a.vx = vx;
     a.vy = vy;
     a.x_off = x_offset;
@@ -662,6 +780,49 @@ static TrainArgs make_args(const float *voxels, const int32_t *num_points, const
     return a;
 }
 
+static Segs host_segs(int64_t m) { return Segs{nullptr, (long long)m, (long long)m, 1}; }
+static Segs dev_segs(const int32_t *counts, int n_seg, int64_t stride) { return Segs{counts, (long long)stride, 0, n_seg}; }
+static int64_t seg_rows(const Segs &s) { return s.counts ? s.n_seg * s.stride : s.host_m; }
+
+// the launches of the forward / backward, for host and device counts alike
+static void launch_forward(const TrainArgs &a, const Layout &L, char *ws, float eps1, float eps2, float *out, float *mean1, float *var1,
+                           float *mean2, float *var2, hipStream_t st) {
+    double *d64 = (double *)(ws + L.d64);
+    float *f32 = (float *)(ws + L.f32);
+    const Segs &sg = a.seg;
+    const int P = a.P;
+    const dim3 grid((unsigned)L.grid), block(kWaves * 64);
+    // layer 1: statistics of the decorated features
+    hipLaunchKernelGGL(stats_pass<1>, grid, block, 0, st, a);
+    reduce(a.part, sg, P, 0, kFin, 1, kFin, nullptr, d64 + D_SUM1, st);
+    reduce(a.part, sg, P, 0, kFin * kFin, 2, kFin, d64 + D_SUM1, d64 + D_CM1, st);
+    hipLaunchKernelGGL((finish_stats<kU1, kFin>), dim3(1), dim3(256), 0, st, a.w1, a.fin, d64 + D_SUM1, d64 + D_CM1, sg, P, eps1, d64 + D_WC1, mean1,
+                       var1, f32 + F_MU1, f32 + F_IS1);
+    // layer 2: statistics of its input rows [a1, max1]
+    hipLaunchKernelGGL(stats_pass<2>, grid, block, 0, st, a);
+    reduce(a.part, sg, P, 0, kU2, 1, kU2, nullptr, d64 + D_SUM2, st);
+    reduce(a.part, sg, P, 0, kU2 * kU2, 2, kU2, d64 + D_SUM2, d64 + D_CM2, st);
+    hipLaunchKernelGGL((finish_stats<kU2, kU2>), dim3(1), dim3(256), 0, st, a.w2, kU2, d64 + D_SUM2, d64 + D_CM2, sg, P, eps2, d64 + D_WC2, mean2,
+                       var2, f32 + F_MU2, f32 + F_IS2);
+    hipLaunchKernelGGL(output_pass, grid, block, 0, st, a, out, (unsigned char *)(ws + L.arg2), (float *)(ws + L.xsel));
+}
+
+static void launch_backward(const TrainArgs &a, const Layout &L, char *ws, const float *dout, float *dw1, float *dgamma1, float *dbeta1, float *dw2,
+                            float *dgamma2, float *dbeta2, hipStream_t st) {
+    double *d64 = (double *)(ws + L.d64);
+    float *f32 = (float *)(ws + L.f32);
+    const unsigned char *arg2 = (const unsigned char *)(ws + L.arg2);
+    const Segs &sg = a.seg;
+    const int P = a.P;
+    const dim3 grid((unsigned)L.grid), block(kWaves * 64);
+    hipLaunchKernelGGL(sparse_pass, grid, block, 0, st, sg, P, dout, arg2, (const float *)(ws + L.xsel), a.part);
+    reduce(a.part, sg, P, 0, 2 * kU2, 0, 0, nullptr, d64 + D_BS, st);
+    hipLaunchKernelGGL(finish_sparse, dim3(1), dim3(256), 0, st, a.w2, a.g2, d64 + D_BS, sg, P, f32, dgamma2, dbeta2);
+    hipLaunchKernelGGL(rows_pass, grid, block, 0, st, a, dout, arg2);
+    reduce(a.part, sg, P, 0, kPartStride, 0, 0, nullptr, d64 + D_BR, st);
+    hipLaunchKernelGGL(finish_rows, dim3(1), dim3(256), 0, st, a.g1, a.g2, a.fin, d64, f32, sg, P, dw1, dgamma1, dbeta1, dw2);
+}
+
 extern "C" int fd_pillar_train_forward(const float *voxels, const int32_t *num_points, const int32_t *coors4, int64_t m, int max_points, int ndim,
                                        int with_distance, float vx, float vy, float x_offset, float y_offset, const float *w1, const float *gamma1,
                                        const float *beta1, int units1, float eps1, const float *w2, const float *gamma2, const float *beta2,
@@ -670,28 +831,12 @@ extern "C" int fd_pillar_train_forward(const float *voxels, const int32_t *num_p
     FD_PT_CHECK("fd_pillar_train_forward");
     FD_REQUIRE(out && mean1 && var1 && mean2 && var2, "fd_pillar_train_forward: null output");
     FD_REQUIRE(eps1 > 0.f && eps2 > 0.f, "fd_pillar_train_forward: eps must be > 0");
-    const Layout L = layout(m);
+    const Segs sg = host_segs(m);
+    const Layout L = layout(seg_rows(sg));
     char *ws = (char *)workspace;
-    TrainArgs a = make_args(voxels, num_points, coors4, m, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
-                            gamma2, beta2, L, ws);
-    hipStream_t st = fd::as_stream(stream_);
-    double *d64 = (double *)(ws + L.d64);
-    float *f32 = (float *)(ws + L.f32);
-    const double n_tot = (double)m * max_points;
-    const dim3 grid((unsigned)L.nb), block(kWaves * 64);
-    // layer 1: statistics of the decorated features
-    hipLaunchKernelGGL(stats_pass<1>, grid, block, 0, st, a);
-    reduce(a.part, L.nb, 0, kFin, 1, kFin, nullptr, n_tot, d64 + D_SUM1, st);
-    reduce(a.part, L.nb, 0, kFin * kFin, 2, kFin, d64 + D_SUM1, n_tot, d64 + D_CM1, st);
-    hipLaunchKernelGGL((finish_stats<kU1, kFin>), dim3(1), dim3(256), 0, st, w1, a.fin, d64 + D_SUM1, d64 + D_CM1, n_tot, eps1, d64 + D_WC1, mean1,
-                       var1, f32 + F_MU1, f32 + F_IS1);
-    // layer 2: statistics of its input rows [a1, max1]
-    hipLaunchKernelGGL(stats_pass<2>, grid, block, 0, st, a);
-    reduce(a.part, L.nb, 0, kU2, 1, kU2, nullptr, n_tot, d64 + D_SUM2, st);
-    reduce(a.part, L.nb, 0, kU2 * kU2, 2, kU2, d64 + D_SUM2, n_tot, d64 + D_CM2, st);
-    hipLaunchKernelGGL((finish_stats<kU2, kU2>), dim3(1), dim3(256), 0, st, w2, kU2, d64 + D_SUM2, d64 + D_CM2, n_tot, eps2, d64 + D_WC2, mean2,
-                       var2, f32 + F_MU2, f32 + F_IS2);
-    hipLaunchKernelGGL(output_pass, grid, block, 0, st, a, out, (unsigned char *)(ws + L.arg2), (float *)(ws + L.xsel));
+    const TrainArgs a = make_args(voxels, num_points, coors4, sg, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
+                                  gamma2, beta2, L, ws);
+    launch_forward(a, L, ws, eps1, eps2, out, mean1, var1, mean2, var2, fd::as_stream(stream_));
     return fd::check_launch("fd_pillar_train_forward");
 }
 
@@ -703,21 +848,62 @@ extern "C" int fd_pillar_train_backward(const float *voxels, const int32_t *num_
     FD_PT_CHECK("fd_pillar_train_backward");
     FD_REQUIRE(dout, "fd_pillar_train_backward: null dout");
     FD_REQUIRE(dw1 && dgamma1 && dbeta1 && dw2 && dgamma2 && dbeta2, "fd_pillar_train_backward: null gradient output");
-    const Layout L = layout(m);
+    const Segs sg = host_segs(m);
+    const Layout L = layout(seg_rows(sg));
     char *ws = (char *)workspace;
-    TrainArgs a = make_args(voxels, num_points, coors4, m, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
-                            gamma2, beta2, L, ws);
-    hipStream_t st = fd::as_stream(stream_);
-    double *d64 = (double *)(ws + L.d64);
-    float *f32 = (float *)(ws + L.f32);
-    const unsigned char *arg2 = (const unsigned char *)(ws + L.arg2);
-    const double n_tot = (double)m * max_points;
-    const dim3 grid((unsigned)L.nb), block(kWaves * 64);
-    hipLaunchKernelGGL(sparse_pass, grid, block, 0, st, (long long)m, L.ppb, dout, arg2, (const float *)(ws + L.xsel), a.part);
-    reduce(a.part, L.nb, 0, 2 * kU2, 0, 0, nullptr, n_tot, d64 + D_BS, st);
-    hipLaunchKernelGGL(finish_sparse, dim3(1), dim3(256), 0, st, w2, gamma2, d64 + D_BS, n_tot, f32, dgamma2, dbeta2);
-    hipLaunchKernelGGL(rows_pass, grid, block, 0, st, a, dout, arg2);
-    reduce(a.part, L.nb, 0, kPartStride, 0, 0, nullptr, n_tot, d64 + D_BR, st);
-    hipLaunchKernelGGL(finish_rows, dim3(1), dim3(256), 0, st, gamma1, gamma2, a.fin, d64, f32, n_tot, dw1, dgamma1, dbeta1, dw2);
+    const TrainArgs a = make_args(voxels, num_points, coors4, sg, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
+                                  gamma2, beta2, L, ws);
+    launch_backward(a, L, ws, dout, dw1, dgamma1, dbeta1, dw2, dgamma2, dbeta2, fd::as_stream(stream_));
     return fd::check_launch("fd_pillar_train_backward");
+}
+
+extern "C" int fd_pillar_train_forward_dev(const float *voxels, const int32_t *num_points, const int32_t *coors4, const int32_t *seg_counts,
+                                           int n_seg, int64_t seg_stride, int max_points, int ndim, int with_distance, float vx, float vy,
+                                           float x_offset, float y_offset, const float *w1, const float *gamma1, const float *beta1, int units1,
+                                           float eps1, const float *w2, const float *gamma2, const float *beta2, int units2, float eps2, float *out,
+                                           float *mean1, float *var1, float *mean2, float *var2, void *workspace, size_t workspace_bytes,
+                                           fd_stream_t stream_) {
+    FD_PT_CHECK_DEV("fd_pillar_train_forward_dev");
+    FD_REQUIRE(out && mean1 && var1 && mean2 && var2, "fd_pillar_train_forward_dev: null output");
+    FD_REQUIRE(eps1 > 0.f && eps2 > 0.f, "fd_pillar_train_forward_dev: eps must be > 0");
+    const Segs sg = dev_segs(seg_counts, n_seg, seg_stride);
+    const Layout L = layout(seg_rows(sg));
+    char *ws = (char *)workspace;
+    const TrainArgs a = make_args(voxels, num_points, coors4, sg, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
+                                  gamma2, beta2, L, ws);
+    launch_forward(a, L, ws, eps1, eps2, out, mean1, var1, mean2, var2, fd::as_stream(stream_));
+    return fd::check_launch("fd_pillar_train_forward_dev");
+}
+
+extern "C" int fd_pillar_train_backward_dev(const float *voxels, const int32_t *num_points, const int32_t *coors4, const int32_t *seg_counts,
+                                            int n_seg, int64_t seg_stride, int max_points, int ndim, int with_distance, float vx, float vy,
+                                            float x_offset, float y_offset, const float *w1, const float *gamma1, const float *beta1, int units1,
+                                            const float *w2, const float *gamma2, const float *beta2, int units2, const float *dout, float *dw1,
+                                            float *dgamma1, float *dbeta1, float *dw2, float *dgamma2, float *dbeta2, void *workspace,
+                                            size_t workspace_bytes, fd_stream_t stream_) {
+    FD_PT_CHECK_DEV("fd_pillar_train_backward_dev");
+    FD_REQUIRE(dout, "fd_pillar_train_backward_dev: null dout");
+    FD_REQUIRE(dw1 && dgamma1 && dbeta1 && dw2 && dgamma2 && dbeta2, "fd_pillar_train_backward_dev: null gradient output");
+    const Segs sg = dev_segs(seg_counts, n_seg, seg_stride);
+    const Layout L = layout(seg_rows(sg));
+    char *ws = (char *)workspace;
+    const TrainArgs a = make_args(voxels, num_points, coors4, sg, max_points, ndim, with_distance, vx, vy, x_offset, y_offset, w1, gamma1, beta1, w2,
+                                  gamma2, beta2, L, ws);
+    launch_backward(a, L, ws, dout, dw1, dgamma1, dbeta1, dw2, dgamma2, dbeta2, fd::as_stream(stream_));
+    return fd::check_launch("fd_pillar_train_backward_dev");
+}
+
+extern "C" int fd_pillar_train_running_stats_dev(const float *mean, const float *var, int channels, double momentum, const int32_t *seg_counts,
+                                                 int n_seg, int64_t seg_stride, int max_points, float *running_mean, float *running_var,
+                                                 int64_t *num_batches_tracked, fd_stream_t stream_) {
+    FD_REQUIRE(mean && var && seg_counts && running_mean && running_var, "fd_pillar_train_running_stats_dev: null argument");
+    FD_REQUIRE(channels >= 1, "fd_pillar_train_running_stats_dev: channels must be >= 1 (got %d)", channels);
+    FD_REQUIRE(momentum >= 0.0 && momentum <= 1.0, "fd_pillar_train_running_stats_dev: momentum must be in [0,1]");
+    FD_REQUIRE(n_seg >= 1 && n_seg <= kMaxSegs, "fd_pillar_train_running_stats_dev: n_seg must be in [1,%d] (got %d)", kMaxSegs, n_seg);
+    FD_REQUIRE(seg_stride >= 1 && seg_stride < (1ll << 30) / n_seg, "fd_pillar_train_running_stats_dev: seg_stride out of range");
+    FD_REQUIRE(max_points >= 1 && max_points <= kMaxP, "fd_pillar_train_running_stats_dev: max_points must be in [1,%d] (got %d)", kMaxP,
+               max_points);
+    hipLaunchKernelGGL(running_stats, dim3(1), dim3(64), 0, fd::as_stream(stream_), dev_segs(seg_counts, n_seg, seg_stride), max_points, mean, var,
+                       channels, momentum, running_mean, running_var, (long long *)num_batches_tracked);
+    return fd::check_launch("fd_pillar_train_running_stats_dev");
 }

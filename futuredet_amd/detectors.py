@@ -262,7 +262,7 @@ class VoxelNet(SingleStageDetector):
         return out
 
 
-    def forward_points_train(self, clouds, voxel_cfg, example, counts=None, static=False, row_caps=None):
+    def forward_points_train(self, clouds, voxel_cfg, example, counts=None, static=False, row_caps=None, bev_map=None):
         """The training twin of forward_points: device clouds -> fused voxeliser with mean features (the TRAIN cap max_voxel_num[0]) ->
         index pyramid -> rows in index order -> backbone.forward_static_train -> neck -> head -> bbox_head.loss(example, preds).  Train mode
         with gradients on; ``example`` is the TargetAssigner's output (hm / ind / mask / cat / anno_box).  ``counts``: per cloud a device
@@ -270,11 +270,12 @@ class VoxelNet(SingleStageDetector):
         data-free bounds) and every kernel takes its count from the device, so the call is issued without waiting for the device
         (solver.StaticTrainStep); an overflowing level is detectable from ``last_level_counts`` and not computed correctly.
         ``static=False``: ONE host read of the level counts sizes the levels exactly; it gives the same bits (bias gradients of the block
-        convolutions: to the last rounding).  Needs backbone.fused_bn; the loss runs without synchronisation with bbox_head.fused_loss."""
+        convolutions: to the last rounding).  Needs backbone.fused_bn; the loss runs without synchronisation with bbox_head.fused_loss.
+        ``bev_map``: the [B, 6, H, W] fp32 second input of a bev_map head (the forecast_n3dtfm configs), handed to the head as it is."""
         if not self.training or not torch.is_grad_enabled():
             raise RuntimeError("forward_points_train is the training path: call .train() and enable gradients")
-        if getattr(self.bbox_head, "bev_map", False):
-            raise NotImplementedError("forward_points_train: a bev_map head takes a second input that this path does not carry")
+        if getattr(self.bbox_head, "bev_map", False) and bev_map is None:
+            raise ValueError("forward_points_train: the head was built with bev_map=True and needs the map (bev_map=[B, 6, H, W])")
         dev = clouds[0].device
         B = len(clouds)
         rng, vs = voxel_cfg["range"], voxel_cfg["voxel_size"]
@@ -303,7 +304,7 @@ class VoxelNet(SingleStageDetector):
             hip_ops.rows_place(i0, coors[sl], mean[sl], cpad, torch.float32, n_dev=nvox[b:b + 1], out=feats0)
         x = bb.forward_static_train(feats0, idx)
         x = self.neck(x)
-        preds = self.bbox_head(x, None)
+        preds = self.bbox_head(x, bev_map)
         return self.bbox_head.loss(example, preds)
 
 
@@ -628,6 +629,48 @@ class PointPillars(SingleStageDetector):
             out = self.bbox_head.predict({"metadata": [None] * B}, preds, self.test_cfg)
         mark_stage("decode")
         return out
+
+    def forward_points_train(self, clouds, voxel_cfg, example, counts=None, static=False, bev_map=None):
+        """The training twin of forward_points, and VoxelNet.forward_points_train's counterpart: device clouds -> per-cloud voxeliser with
+        point slots (the TRAIN cap max_voxel_num[0]) -> train-mode pillar reader -> scatter -> neck -> head -> bbox_head.loss(example,
+        preds).  Train mode with gradients on; ``example`` is the TargetAssigner's output; ``counts``: per cloud a device int32[1] with
+        its number of valid rows; ``bev_map`` as in VoxelNet.forward_points_train.
+        ``static=True``: no host read anywhere -- the reader (PillarFeatureNet.forward_train_static), its running statistics and the
+        scatter with its backward take the pillar counts from the device.  ``static=False``: ONE host read of the pillar counts, the
+        pillars compacted into one buffer, the host-count reader: the same bits.  Both set ``last_level_counts`` to the device
+        tensor of the pillar counts [B]."""
+        if not self.training or not torch.is_grad_enabled():
+            raise RuntimeError("forward_points_train is the training path: call .train() and enable gradients")
+        if getattr(self.bbox_head, "bev_map", False) and bev_map is None:
+            raise ValueError("forward_points_train: the head was built with bev_map=True and needs the map (bev_map=[B, 6, H, W])")
+        dev = clouds[0].device
+        B = len(clouds)
+        rng, vs = voxel_cfg["range"], voxel_cfg["voxel_size"]
+        mv = voxel_cfg["max_voxel_num"]
+        cap = int(mv[0] if isinstance(mv, (list, tuple)) else mv)  # train cap (preprocess.py:256-258)
+        max_points = int(voxel_cfg["max_points_in_voxel"])
+        ndim = clouds[0].shape[1]
+        voxels = torch.empty((B, cap, max_points, ndim), dtype=torch.float32, device=dev)
+        coors = torch.empty((B, cap, 4), dtype=torch.int32, device=dev)
+        npts = torch.empty((B, cap), dtype=torch.int32, device=dev)
+        nvox = torch.empty((B,), dtype=torch.int32, device=dev)  # written by every fd_voxelize call, empty clouds included
+        for b, pts in enumerate(clouds):
+            hip_ops.voxelize(pts, vs, rng, max_points, cap, batch_idx=b, want_voxels=True, coor_cols=4,
+                             out=dict(voxels=voxels[b], coors=coors[b], num_points=npts[b], num_voxels=nvox[b:b + 1]),
+                             n_points_dev=None if counts is None else counts[b])
+        self.__dict__["last_level_counts"] = nvox
+        grid = np.round((np.array(rng[3:], np.float32) - np.array(rng[:3], np.float32)) / np.array(vs, np.float32)).astype(np.int64)
+        if static:
+            feats = self.reader.forward_train_static(voxels, npts, coors, nvox)
+            canvas = self.backbone.forward_static(feats, coors.view(B * cap, 4), nvox, B, grid)
+        else:
+            n = [min(max(int(v), 0), cap) for v in nvox.tolist()]  # the one host read
+            feats = self.reader(torch.cat([voxels[b, :n[b]] for b in range(B)]), torch.cat([npts[b, :n[b]] for b in range(B)]),
+                                torch.cat([coors[b, :n[b]] for b in range(B)]))
+            canvas = self.backbone(feats, torch.cat([coors[b, :n[b]] for b in range(B)]), B, grid)
+        x = self.neck(canvas)
+        preds = self.bbox_head(x, bev_map)
+        return self.bbox_head.loss(example, preds)
 
 
 @DETECTORS.register_module

@@ -1250,9 +1250,97 @@ def pillar_train_backward(dout, voxels, num_points, coors4, geom, w1, g1, b1, w2
     return dw1, dg1, db1, dw2, dg2, db2
 
 
-def pillar_scatter_backward(dcanvas, coors4):
+def _pillar_train_dev_args(voxels, num_points, coors4, seg_counts, geom, w1, g1, b1, w2, g2, b2, with_distance):
+    """Checks and leading arguments of the device-count entries: voxels [B, cap, P, ndim] (or [B * cap, P, ndim] with
+    seg_counts [B]), num_points [B, cap], coors4 [B, cap, 4], seg_counts int32[B] on the device."""
+    voxels = _dev(voxels, "voxels", torch.float32)
+    seg_counts = _dev(seg_counts, "seg_counts", torch.int32)
+    if seg_counts.dim() != 1 or not 1 <= seg_counts.numel() <= 16:
+        raise FutureDetHipError("pillar_train (device counts): seg_counts must be int32[B] with 1 <= B <= 16, got %s" % (tuple(seg_counts.shape),))
+    B = seg_counts.numel()
+    if voxels.dim() == 4:
+        voxels = voxels.reshape(-1, voxels.shape[2], voxels.shape[3])
+    rows, P, ndim = voxels.shape
+    if rows < B or rows % B:
+        raise FutureDetHipError("pillar_train (device counts): %d voxel rows are not %d segments of equal size" % (rows, B))
+    num_points = _dev(num_points, "num_points", torch.int32)
+    coors4 = _dev(coors4, "coors4", torch.int32)
+    if num_points.numel() != rows or coors4.numel() != rows * 4:
+        raise FutureDetHipError("pillar_train (device counts): num_points %s / coors4 %s do not match %d voxel rows"
+                                % (tuple(num_points.shape), tuple(coors4.shape), rows))
+    for t, name in ((w1, "w1"), (g1, "gamma1"), (b1, "beta1"), (w2, "w2"), (g2, "gamma2"), (b2, "beta2")):
+        _dev(t, name, torch.float32)
+    return [_p(voxels), _p(num_points), _p(coors4), _p(seg_counts), B, rows // B, P, ndim, int(bool(with_distance)),
+            float(geom[0]), float(geom[1]), float(geom[2]), float(geom[3])]
+
+
+def pillar_train_forward_dev(voxels, num_points, coors4, seg_counts, geom, w1, g1, b1, eps1, w2, g2, b2, eps2, with_distance=False,
+                             out=None, workspace=None):
+    """fd_pillar_train_forward_dev: pillar_train_forward on B segments of ``cap`` rows whose pillar counts are on the device
+    (seg_counts int32[B]); no host read.  Returns (out [B * cap, 64] with zeros behind the counts, mean1, var1, mean2, var2,
+    workspace): the bits of pillar_train_forward on the compacted pillars."""
+    L = _lib.load()
+    args = _pillar_train_dev_args(voxels, num_points, coors4, seg_counts, geom, w1, g1, b1, w2, g2, b2, with_distance)
+    rows, P = args[4] * args[5], args[6]
+    dev = voxels.device
+    nbytes = L.fd_pillar_train_workspace_bytes(rows, P)
+    if workspace is None:
+        workspace = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((rows, w2.shape[0]), dtype=torch.float32, device=dev)
+    u1, u2 = w1.shape[0], w2.shape[0]
+    stats = torch.empty((2 * u1 + 2 * u2,), dtype=torch.float32, device=dev)
+    mean1, var1, mean2, var2 = stats[:u1], stats[u1:2 * u1], stats[2 * u1:2 * u1 + u2], stats[2 * u1 + u2:]
+    check(L.fd_pillar_train_forward_dev(*args, _p(w1), _p(g1), _p(b1), u1, float(eps1), _p(w2), _p(g2), _p(b2), u2, float(eps2),
+                                        _p(_dev(out, "out", torch.float32)), _p(mean1), _p(var1), _p(mean2), _p(var2), _p(workspace),
+                                        workspace.numel(), _stream()), "fd_pillar_train_forward_dev")
+    return out, mean1, var1, mean2, var2, workspace
+
+
+def pillar_train_backward_dev(dout, voxels, num_points, coors4, seg_counts, geom, w1, g1, b1, w2, g2, b2, workspace, with_distance=False):
+    """fd_pillar_train_backward_dev: dout [B * cap, 64] (rows behind the counts are not read) -> the six gradients; ``workspace``
+    as the matching pillar_train_forward_dev left it."""
+    L = _lib.load()
+    args = _pillar_train_dev_args(voxels, num_points, coors4, seg_counts, geom, w1, g1, b1, w2, g2, b2, with_distance)
+    dout = _dev(dout, "dout", torch.float32)
+    assert tuple(dout.shape) == (args[4] * args[5], w2.shape[0]), (tuple(dout.shape), args[4] * args[5])
+    dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+    dg1, db1, dg2, db2 = torch.empty_like(g1), torch.empty_like(b1), torch.empty_like(g2), torch.empty_like(b2)
+    check(L.fd_pillar_train_backward_dev(*args, _p(w1), _p(g1), _p(b1), w1.shape[0], _p(w2), _p(g2), _p(b2), w2.shape[0], _p(dout),
+                                         _p(dw1), _p(dg1), _p(db1), _p(dw2), _p(dg2), _p(db2), _p(workspace), workspace.numel(),
+                                         _stream()), "fd_pillar_train_backward_dev")
+    return dw1, dg1, db1, dw2, dg2, db2
+
+
+def pillar_train_running_stats_dev(mean, var, momentum, seg_counts, seg_stride, max_points, running_mean, running_var,
+                                   num_batches_tracked=None):
+    """fd_pillar_train_running_stats_dev: torch's BatchNorm running-statistics rule in place, n = max_points * sum of the clamped
+    seg_counts read on the device (nothing happens for n < 2).  ``momentum`` is a number: the cumulative average (None) needs
+    num_batches_tracked on the host."""
+    L = _lib.load()
+    if momentum is None:
+        raise NotImplementedError("pillar_train_running_stats_dev: momentum=None (cumulative average) is not implemented on the "
+                                  "device-count path")
+    mean, var = _dev(mean, "mean", torch.float32), _dev(var, "var", torch.float32)
+    seg_counts = _dev(seg_counts, "seg_counts", torch.int32)
+    running_mean, running_var = _dev(running_mean, "running_mean", torch.float32), _dev(running_var, "running_var", torch.float32)
+    c = mean.numel()
+    if not (var.numel() == running_mean.numel() == running_var.numel() == c):
+        raise FutureDetHipError("pillar_train_running_stats_dev: mean, var and the running buffers must have one length")
+    if num_batches_tracked is not None:
+        num_batches_tracked = _dev(num_batches_tracked, "num_batches_tracked", torch.int64)
+    check(L.fd_pillar_train_running_stats_dev(_p(mean), _p(var), c, float(momentum), _p(seg_counts), seg_counts.numel(), int(seg_stride),
+                                              int(max_points), _p(running_mean), _p(running_var), _p(num_batches_tracked), _stream()),
+          "fd_pillar_train_running_stats_dev")
+    for buf in (running_mean, running_var, num_batches_tracked):
+        if buf is not None:
+            torch.autograd.graph.increment_version(buf)  # written behind torch's back: derived-weight caches key on the version
+
+
+def pillar_scatter_backward(dcanvas, coors4, n_dev=None):
     """Backward of PointPillarsScatter: d(pillar row m) = dcanvas[b, :, y, x] for coors4[m] = (b, 0, y, x) -- fd_dense_gather with D = 1
-    on any canvas strides (NCHW or channels-last).  Returns [M, C] float32."""
+    on any canvas strides (NCHW or channels-last).  Returns [M, C] float32.  ``n_dev``: device int32[1] count of the live rows of
+    coors4; the rows behind it are not read and get gradient 0."""
     L = _lib.load()
     if not (isinstance(dcanvas, torch.Tensor) and dcanvas.is_cuda and dcanvas.dtype == torch.float32):
         raise FutureDetHipError("pillar_scatter_backward: dcanvas must be a float32 tensor on the HIP device")
@@ -1260,7 +1348,9 @@ def pillar_scatter_backward(dcanvas, coors4):
     n, c = coors4.shape[0], dcanvas.shape[1]
     feats = torch.empty((max(n, 1), c), dtype=torch.float32, device=dcanvas.device)[:n]
     sb, sc, sy, sx = dcanvas.stride()
-    check(L.fd_dense_gather(_p(dcanvas), sb, sc, sy, sx, 1, _p(coors4), n, None, c, _p(feats), _stream()), "fd_dense_gather")
+    if n_dev is not None:
+        n_dev = _dev(n_dev, "n_dev", torch.int32)
+    check(L.fd_dense_gather(_p(dcanvas), sb, sc, sy, sx, 1, _p(coors4), n, _p(n_dev), c, _p(feats), _stream()), "fd_dense_gather")
     return feats
 
 

@@ -197,6 +197,15 @@ SIGNATURES = {
     "fd_pillar_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
                                          c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_pillar_train_forward_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_int, c_float, c_float,
+                                            c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                            c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_pillar_train_backward_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_int, c_float, c_float,
+                                             c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
+    "fd_pillar_train_running_stats_dev": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_int, c_i64, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
     "fd_targets_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "fd_assign_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(TargetsCfg), c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -52,7 +52,9 @@ class PillarFeatureNet(nn.Module):
     (fd_pillar_encode) with BatchNorm folded from the running statistics.  In training mode (the shipped stack, two PFN layers
     32 -> 64, fp32) it runs on fd_pillar_train_forward / fd_pillar_train_backward: BatchNorm on batch statistics over every
     point slot of the batch, gradients for both layers' Linear and BatchNorm parameters, and the running statistics updated
-    in place with the BatchNorm modules' own momentum.  The torch modules only define the parameters / state_dict."""
+    in place with the BatchNorm modules' own momentum.  ``forward_train_static`` is the same training form for a fixed-capacity batch
+    whose pillar counts stay on the device (fd_pillar_train_forward_dev / _backward_dev / _running_stats_dev): no host read, the same
+    bits.  The torch modules only define the parameters / state_dict."""
 
     def __init__(self, num_input_features=4, num_filters=(64,), with_distance=False, voxel_size=(0.2, 0.2, 4),
                  pc_range=(0, -40, -3, 70.4, 40, 1), norm_cfg=None):
@@ -97,7 +99,8 @@ class PillarFeatureNet(nn.Module):
                                      with_distance=self._with_distance, out_dtype=self.compute_dtype)
 
 
-    def _forward_train(self, features, num_voxels, coors):
+    def _train_spec(self):
+        """what both training forms check and hand to the kernels: (layer 1, layer 2, (geometry, eps1, eps2, with_distance))"""
         if self.compute_dtype != torch.float32:
             raise NotImplementedError("PillarFeatureNet: training runs in fp32 only; the %s reader is inference-only (set compute_dtype = "
                                       "torch.float32 to train)" % self.compute_dtype)
@@ -106,9 +109,12 @@ class PillarFeatureNet(nn.Module):
             raise NotImplementedError("PillarFeatureNet: training supports the shipped PFN stack num_filters=[64, 64] (units 32 -> 64, "
                                       "fd_pillar_train_forward), not units %s" % units)
         l1, l2 = self.pfn_layers
-        n1, n2 = l1.norm, l2.norm
         geom = (self.vx, self.vy, self.x_offset, self.y_offset)
-        spec = (geom, n1.eps, n2.eps, self._with_distance)
+        return l1, l2, (geom, l1.norm.eps, l2.norm.eps, self._with_distance)
+
+    def _forward_train(self, features, num_voxels, coors):
+        l1, l2, spec = self._train_spec()
+        n1, n2 = l1.norm, l2.norm
         voxels = features.float().contiguous()
         out, stats = _PillarTrain.apply(voxels, num_voxels.int().contiguous(), coors.int().contiguous(), l1.linear.weight.contiguous(),
                                         n1.weight.contiguous(), n1.bias.contiguous(), l2.linear.weight.contiguous(), n2.weight.contiguous(),
@@ -118,6 +124,33 @@ class PillarFeatureNet(nn.Module):
             u1 = n1.num_features
             for bn, mean, var in ((n1, stats[:u1], stats[u1:2 * u1]), (n2, stats[2 * u1:2 * u1 + n2.num_features], stats[2 * u1 + n2.num_features:])):
                 _update_running_stats(bn, mean, var, n)
+        return out
+
+    def forward_train_static(self, features, num_voxels, coors, counts):
+        """The training form with the pillar counts on the device, one call for the whole batch: features [B, cap, P, ndim],
+        num_voxels [B, cap], coors [B, cap, 4], counts int32[B] on the device (sample b's pillars are its first counts[b] rows; the
+        rows behind may hold anything).  Returns [B * cap, 64] with zeros behind the counts -- on the live rows, and in every gradient
+        and batch statistic, the bits of ``forward`` on the compacted pillars -- and updates the running statistics on the device
+        (fd_pillar_train_running_stats_dev).  Nothing waits for the device."""
+        l1, l2, spec = self._train_spec()
+        n1, n2 = l1.norm, l2.norm
+        for bn in (n1, n2):
+            if bn.track_running_stats and bn.running_mean is not None and bn.momentum is None:
+                raise NotImplementedError("PillarFeatureNet.forward_train_static: momentum=None (cumulative average) needs "
+                                          "num_batches_tracked on the host; set a momentum (every shipped norm_cfg has 0.01)")
+        if features.dim() != 4 or counts.dim() != 1 or counts.shape[0] != features.shape[0]:
+            raise ValueError("forward_train_static: features [B, cap, P, ndim] with counts [B], got %s and %s"
+                             % (tuple(features.shape), tuple(counts.shape)))
+        cap, P = features.shape[1], features.shape[2]
+        out, stats = _PillarTrainStatic.apply(features.float().contiguous(), num_voxels.int().contiguous(), coors.int().contiguous(),
+                                              counts.int().contiguous(), l1.linear.weight.contiguous(), n1.weight.contiguous(),
+                                              n1.bias.contiguous(), l2.linear.weight.contiguous(), n2.weight.contiguous(),
+                                              n2.bias.contiguous(), spec)
+        u1, u2 = n1.num_features, n2.num_features
+        for bn, mean, var in ((n1, stats[:u1], stats[u1:2 * u1]), (n2, stats[2 * u1:2 * u1 + u2], stats[2 * u1 + u2:])):
+            if bn.track_running_stats and bn.running_mean is not None:
+                hip_ops.pillar_train_running_stats_dev(mean, var, bn.momentum, counts, cap, P, bn.running_mean, bn.running_var,
+                                                       bn.num_batches_tracked)
         return out
 
 
@@ -159,6 +192,34 @@ class _PillarTrain(torch.autograd.Function):
                                               with_distance=wd)
         ctx.inputs = ctx.ws = None
         return (None, None, None) + tuple(grads) + (None,)
+
+
+class _PillarTrainStatic(torch.autograd.Function):
+    """_PillarTrain over fd_pillar_train_forward_dev / _backward_dev: inputs [B, cap, ...] with the pillar counts [B] on the device.
+    Returns (out [B * cap, 64], stats [192])."""
+
+    @staticmethod
+    def forward(ctx, voxels, num_points, coors4, counts, w1, g1, b1, w2, g2, b2, spec):
+        geom, eps1, eps2, wd = spec
+        out, mean1, var1, mean2, var2, ws = hip_ops.pillar_train_forward_dev(voxels, num_points, coors4, counts, geom, w1, g1, b1, eps1,
+                                                                             w2, g2, b2, eps2, with_distance=wd)
+        stats = torch.cat([mean1, var1, mean2, var2])
+        ctx.inputs = (voxels, num_points, coors4, counts, w1, g1, b1, w2, g2, b2)
+        ctx.ws = ws
+        ctx.spec = spec
+        ctx.mark_non_differentiable(stats)
+        return out, stats
+
+    @staticmethod
+    def backward(ctx, dout, dstats):
+        voxels, num_points, coors4, counts, w1, g1, b1, w2, g2, b2 = ctx.inputs
+        geom, _, _, wd = ctx.spec
+        if dout is None:
+            dout = torch.zeros((voxels.shape[0] * voxels.shape[1], w2.shape[0]), dtype=torch.float32, device=voxels.device)
+        grads = hip_ops.pillar_train_backward_dev(dout.float().contiguous(), voxels, num_points, coors4, counts, geom, w1, g1, b1, w2, g2,
+                                                  b2, ctx.ws, with_distance=wd)
+        ctx.inputs = ctx.ws = None
+        return (None, None, None, None) + tuple(grads) + (None,)
 
 
 def _drop_packed(module, incompatible_keys=None):

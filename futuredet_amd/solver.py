@@ -334,61 +334,36 @@ def train_steps(model, batches, optimizer, scheduler, grad_clip=None, start_iter
         yield losses
 
 
-class StaticTrainStep(object):
-    """One whole training iteration of a VoxelNet -- zero_grad, voxeliser, index pyramid, AssignLabel's targets, sparse backbone, RPN,
-    CenterHead, loss, backward, clipping and Adam -- issued without ever waiting for the device: detectors.StaticStep's counterpart for
-    training, without its graph (see ``graph`` below).  Shapes are static: the clouds live in fixed-capacity buffers with
-    their row counts on the device, the ground truth is padded to [B, T, max_gt, 12], the sparse levels are sized by row capacities
-    and every kernel takes its count from device memory (VoxelNet.forward_points_train(static=True)); lr, beta1 and the other four
-    scalars of the optimiser reach the kernels through a device record that is refreshed before every step
-    (FusedAdam.step(hyper=...)): the launches do not bake the schedule in.
+class _StaticTrainBase(object):
+    """What the sync-free training steps share: the static inputs (clouds and their counts, padded ground truth, the map of a bev_map
+    head), the ring of pinned staging buffers, the device record of the optimiser's scalars, the iteration body and the restoring
+    warm-up.  A subclass says which detector it takes (_check_model) and how one forward pass is issued (_forward)."""
 
-        step = StaticTrainStep(model, cfg.voxel_generator, assigner, optimizer, scheduler, grad_clip, capacity=400000, batch_size=2)
-        step.warm_up(batches)                 # eager steps: conv plan choices + level counts; leaves model and optimiser as they were
-        for batch in loader:                  # batch: dict(clouds=[B device tensors [N_i, ndim]], gt_boxes=[B, T, n, 12] fp32,
-            losses = step(batch)              #             gt_counts=[B, T] int32, gt_classes=[B, T, n] int32[, gt_trajectory])
+    name = "_StaticTrainBase"
 
-    ``step(batch)`` runs scheduler.step(iteration), uploads the six scalars, copies the batch into the static inputs and issues the
-    launches.  It returns the model's loss dict (device tensors) with ``total_norm`` when clipping is on.
+    def _check_model(self, model):
+        raise NotImplementedError
 
-    Row capacities (``row_caps="auto"``): ``headroom`` x the largest level counts of the warm-up batches + 4096.  A batch that needs
-    more rows on some level sets a flag ON THE DEVICE (fd_levels_overflow) that makes the optimiser step of that iteration a no-op:
-    parameters, moments and step counts stay.  With ``check=True`` (default) the level counts are read back after the step -- the one
-    synchronisation of the call -- and an overflowed batch is re-run on the host-sized path (forward_points_train(static=False))
-    with the same scheduler iteration, so step counts and the iteration advance exactly once.  ``check=False`` keeps the call
-    asynchronous; ask ``overflowed()`` later.  What an overflowed step leaves behind: the BatchNorm running statistics (and
-    num_batches_tracked) were updated once by its forward pass, on a truncated but valid batch, before the re-run updates them again.
+    def _forward(self, clouds, counts, example, static):
+        raise NotImplementedError
 
-    ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
-    device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward
-    included -- crashed the HIP runtime when the capture was ended (torch 2.10 on ROCm 7, MI355X; DESIGN.md "The sync-free training
-    step"), so the capture is not part of the class; ``graph=True`` raises NotImplementedError.  One StaticTrainStep belongs to one stream."""
+    def _guard(self, static, level_counts):
+        """the device flag that turns this iteration's optimiser step into a no-op, or None"""
+        return None
 
-    def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
-                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False):
-        from .detectors import VoxelNet
-
-        if not isinstance(model, VoxelNet):
-            raise NotImplementedError("StaticTrainStep: %s is not a VoxelNet; the static training step covers the sparse-backbone detector "
-                                      "only (PointPillars trains through train_steps)" % type(model).__name__)
-        head, bb = model.bbox_head, model.backbone
-        if getattr(head, "dcn_head", False):
-            raise NotImplementedError("StaticTrainStep: a dcn_head CenterHead is not covered (dcn_head=True); train it through train_steps")
-        if not getattr(bb, "fused_bn", False):
-            raise ValueError("StaticTrainStep: backbone.fused_bn is off; torch's BatchNorm1d cannot take its row count from the device "
-                             "(set model.backbone.fused_bn = True)")
+    def _init_common(self, model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph):
+        name = self.name
+        self._check_model(model)
+        head = model.bbox_head
         if not getattr(head, "fused_loss", False):
-            raise ValueError("StaticTrainStep: bbox_head.fused_loss is off; the torch loss copies its terms to the host "
-                             "(set model.bbox_head.fused_loss = True)")
-        if getattr(head, "bev_map", False):
-            raise NotImplementedError("StaticTrainStep: a bev_map head takes a second input that the step does not carry")
+            raise ValueError("%s: bbox_head.fused_loss is off; the torch loss copies its terms to the host "
+                             "(set model.bbox_head.fused_loss = True)" % name)
         self.model, self.voxel_cfg, self.assigner, self.optimizer, self.scheduler = model, voxel_cfg, assigner, optimizer, scheduler
         if graph:
-            raise NotImplementedError("StaticTrainStep: graph=True is not available -- ending the capture of the whole step crashed the HIP "
-                                      "runtime; the step is issued eagerly without host synchronisation (graph=False)")
+            raise NotImplementedError("%s: graph=True is not available -- ending the capture of the whole step crashed the HIP "
+                                      "runtime; the step is issued eagerly without host synchronisation (graph=False)" % name)
         self.grad_clip = grad_clip
         parse_grad_clip(grad_clip)
-        self.row_caps_mode, self.headroom = row_caps, float(headroom)
         self.B, self.capacity, self.ndim = int(batch_size), int(capacity), int(ndim)
         self.T = int(timesteps if timesteps is not None else getattr(head, "timesteps", 1))
         self.max_gt = int(max_gt if max_gt is not None else assigner.max_objs)
@@ -401,12 +376,12 @@ class StaticTrainStep(object):
         self.gt_counts = torch.zeros((B, T), dtype=torch.int32, device=dev)
         self.gt_classes = torch.zeros((B, T, n), dtype=torch.int32, device=dev)
         self.gt_trajectory = torch.zeros((B, T, n), dtype=torch.int32, device=dev) if assigner.extra_sets else None
+        # the second input of a bev_map head (forecast_n3dtfm): [B, 6, H, W] on the head's feature map, filled from batch["bev_map"]
+        self.bev = torch.zeros((B, 6, assigner.H, assigner.W), dtype=torch.float32, device=dev) if getattr(head, "bev_map", False) else None
         self.targets = assigner.outputs(B, T, dev)
         self.hyper = torch.zeros((len(hip_ops.HYPER_FIELDS),), dtype=torch.float64, device=dev)
-        self.skip = torch.zeros((1,), dtype=torch.int32, device=dev)
         self._ring, self._slot = None, 0
         self.iteration = 0
-        self.expected, self.caps, self.caps_dev = None, None, None
         self.outputs, self.level_counts = None, None
 
     def __del__(self):
@@ -414,10 +389,6 @@ class StaticTrainStep(object):
             hip_ops.workspace.release(id(self))
         except Exception:
             pass
-
-    def reset(self):
-        """drops the row capacities (the next call derives them again from ``row_caps`` and the warm-up counts)"""
-        self.caps, self.caps_dev, self.outputs = None, None, None
 
     # -- inputs
     def _pinned(self):
@@ -435,6 +406,13 @@ class StaticTrainStep(object):
         clouds = batch["clouds"]
         if len(clouds) != self.B:
             raise ValueError("the step was built for batches of %d clouds, got %d" % (self.B, len(clouds)))
+        if self.bev is not None:
+            bev = batch.get("bev_map")
+            if bev is None:
+                raise ValueError("the head was built with bev_map=True: the batch needs \"bev_map\" [%d, 6, %d, %d]"
+                                 % (self.B, self.bev.shape[2], self.bev.shape[3]))
+            if tuple(bev.shape) != tuple(self.bev.shape):
+                raise ValueError("bev_map %s does not fit the step's %s buffer" % (tuple(bev.shape), tuple(self.bev.shape)))
         if self.scheduler is not None:
             self.scheduler.step(iteration)
         slot = self._pinned()
@@ -459,6 +437,8 @@ class StaticTrainStep(object):
         self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
         if self.gt_trajectory is not None:
             self.gt_trajectory[:, :, :n].copy_(batch["gt_trajectory"], non_blocking=True)
+        if self.bev is not None:
+            self.bev.copy_(batch["bev_map"], non_blocking=True)
 
     # -- the step
     def _body(self, static):
@@ -470,13 +450,11 @@ class StaticTrainStep(object):
         example = self.assigner(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_trajectory, out=self.targets, check=False)
         clouds = [self.points[b] for b in range(self.B)]
         counts = [self.counts[b:b + 1] for b in range(self.B)]
-        losses = m.forward_points_train(clouds, self.voxel_cfg, example, counts=counts, static=static, row_caps=self.caps if static else None)
+        losses = self._forward(clouds, counts, example, static)
         level_counts = m.last_level_counts
-        guarded = static and self.caps_dev is not None
-        if guarded:
-            hip_ops.levels_overflow(level_counts, self.caps_dev, self.skip)
+        skip = self._guard(static, level_counts)
         sum(losses["loss"]).backward()
-        total_norm = opt.step(grad_clip=self.grad_clip, hyper=self.hyper, skip=self.skip if guarded else None)
+        total_norm = opt.step(grad_clip=self.grad_clip, hyper=self.hyper, skip=skip)
         losses = dict(losses)
         if total_norm is not None:
             losses["total_norm"] = total_norm
@@ -508,10 +486,8 @@ class StaticTrainStep(object):
 
         return _Restore()
 
-    def warm_up(self, batches):
-        """Eager steps on the host-sized path (forward_points_train(static=False)) over representative batches: lets the dense
-        convolutions pick their kernels, fixes the optimiser's gradient set and pointer table, and records the largest level counts
-        (the capacities of row_caps="auto").  The model, the optimiser and the iteration count are restored afterwards."""
+    def _warm(self, batches):
+        """eager steps (static=False) over ``batches`` inside _restoring(); returns the largest level counts seen, or None"""
         seen = None
         with self._restoring():
             for batch in batches:
@@ -520,8 +496,83 @@ class StaticTrainStep(object):
                 counts = [int(v) for v in self.model.last_level_counts]
                 seen = counts if seen is None else [max(a, b) for a, b in zip(seen, counts)]
         if seen is None:
-            raise ValueError("StaticTrainStep.warm_up needs at least one batch")
-        self.expected = seen
+            raise ValueError("%s.warm_up needs at least one batch" % self.name)
+        return seen
+
+
+class StaticTrainStep(_StaticTrainBase):
+    """One whole training iteration of a VoxelNet -- zero_grad, voxeliser, index pyramid, AssignLabel's targets, sparse backbone, RPN,
+    CenterHead, loss, backward, clipping and Adam -- issued without ever waiting for the device: detectors.StaticStep's counterpart for
+    training, without its graph (see ``graph`` below).  Shapes are static: the clouds live in fixed-capacity buffers with
+    their row counts on the device, the ground truth is padded to [B, T, max_gt, 12], the sparse levels are sized by row capacities
+    and every kernel takes its count from device memory (VoxelNet.forward_points_train(static=True)); lr, beta1 and the other four
+    scalars of the optimiser reach the kernels through a device record that is refreshed before every step
+    (FusedAdam.step(hyper=...)): the launches do not bake the schedule in.
+
+        step = StaticTrainStep(model, cfg.voxel_generator, assigner, optimizer, scheduler, grad_clip, capacity=400000, batch_size=2)
+        step.warm_up(batches)                 # eager steps: conv plan choices + level counts; leaves model and optimiser as they were
+        for batch in loader:                  # batch: dict(clouds=[B device tensors [N_i, ndim]], gt_boxes=[B, T, n, 12] fp32,
+            losses = step(batch)              #             gt_counts=[B, T] int32, gt_classes=[B, T, n] int32[, gt_trajectory])
+
+    ``step(batch)`` runs scheduler.step(iteration), uploads the six scalars, copies the batch into the static inputs and issues the
+    launches.  It returns the model's loss dict (device tensors) with ``total_norm`` when clipping is on.  For a bev_map head (the
+    forecast_n3dtfm configs) the batch also carries ``bev_map`` [B, 6, H, W] fp32 on the head's feature map; the step keeps it in a
+    static buffer (``self.bev``) that the warm-up and the overflow re-run read too, and a batch without it raises ValueError.
+
+    Row capacities (``row_caps="auto"``): ``headroom`` x the largest level counts of the warm-up batches + 4096.  A batch that needs
+    more rows on some level sets a flag ON THE DEVICE (fd_levels_overflow) that makes the optimiser step of that iteration a no-op:
+    parameters, moments and step counts stay.  With ``check=True`` (default) the level counts are read back after the step -- the one
+    synchronisation of the call -- and an overflowed batch is re-run on the host-sized path (forward_points_train(static=False))
+    with the same scheduler iteration, so step counts and the iteration advance exactly once.  ``check=False`` keeps the call
+    asynchronous; ask ``overflowed()`` later.  What an overflowed step leaves behind: the BatchNorm running statistics (and
+    num_batches_tracked) were updated once by its forward pass, on a truncated but valid batch, before the re-run updates them again.
+
+    ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
+    device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward
+    included -- crashed the HIP runtime when the capture was ended (torch 2.10 on ROCm 7, MI355X; DESIGN.md "The sync-free training
+    step"), so the capture is not part of the class; ``graph=True`` raises NotImplementedError.  One StaticTrainStep belongs to one stream."""
+
+    name = "StaticTrainStep"
+
+    def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
+                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False):
+        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph)
+        self.row_caps_mode, self.headroom = row_caps, float(headroom)
+        self.skip = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        self.expected, self.caps, self.caps_dev = None, None, None
+
+    def _check_model(self, model):
+        from .detectors import VoxelNet
+
+        if not isinstance(model, VoxelNet):
+            raise NotImplementedError("StaticTrainStep: %s is not a VoxelNet; the static training step covers the sparse-backbone detector "
+                                      "only (PointPillars trains through StaticPillarsTrainStep)" % type(model).__name__)
+        head, bb = model.bbox_head, model.backbone
+        if getattr(head, "dcn_head", False):
+            raise NotImplementedError("StaticTrainStep: a dcn_head CenterHead is not covered (dcn_head=True); train it through train_steps")
+        if not getattr(bb, "fused_bn", False):
+            raise ValueError("StaticTrainStep: backbone.fused_bn is off; torch's BatchNorm1d cannot take its row count from the device "
+                             "(set model.backbone.fused_bn = True)")
+
+    def reset(self):
+        """drops the row capacities (the next call derives them again from ``row_caps`` and the warm-up counts)"""
+        self.caps, self.caps_dev, self.outputs = None, None, None
+
+    def _forward(self, clouds, counts, example, static):
+        return self.model.forward_points_train(clouds, self.voxel_cfg, example, counts=counts, static=static,
+                                               row_caps=self.caps if static else None, bev_map=self.bev)
+
+    def _guard(self, static, level_counts):
+        if not (static and self.caps_dev is not None):
+            return None
+        hip_ops.levels_overflow(level_counts, self.caps_dev, self.skip)
+        return self.skip
+
+    def warm_up(self, batches):
+        """Eager steps on the host-sized path (forward_points_train(static=False)) over representative batches: lets the dense
+        convolutions pick their kernels, fixes the optimiser's gradient set and pointer table, and records the largest level counts
+        (the capacities of row_caps="auto").  The model, the optimiser and the iteration count are restored afterwards."""
+        self.expected = self._warm(batches)
         self.reset()
 
     def _set_caps(self):
@@ -561,5 +612,59 @@ class StaticTrainStep(object):
         return any(n > c for n, c in zip(lc, self.caps))
 
 
+class StaticPillarsTrainStep(_StaticTrainBase):
+    """StaticTrainStep's counterpart for PointPillars: zero_grad, per-cloud voxeliser with point slots, targets, the train-mode pillar
+    reader with its counts on the device, scatter, RPN, CenterHead, loss, backward, clipping and Adam, issued without ever waiting for
+    the device (PointPillars.forward_points_train(static=True)).  The batch contract, the staging ring, the device record of the
+    optimiser's scalars and ``warm_up`` are StaticTrainStep's:
+
+        step = StaticPillarsTrainStep(model, cfg.voxel_generator, assigner, optimizer, scheduler, grad_clip, capacity=400000, batch_size=2)
+        step.warm_up(batches)                 # eager steps (static=False); leaves model and optimiser as they were
+        for batch in loader:
+            losses = step(batch)
+
+    There are no row capacities and no overflow guard: the voxeliser caps the pillars of a cloud at max_voxel_num[0] and every buffer
+    has that size, so ``overflowed()`` is False and ``check`` reads nothing back.  Needs bbox_head.fused_loss; a bev_map head takes
+    batch["bev_map"]; neck / bbox_head train_dtype = torch.bfloat16 and the dense fused_bn switches work as in train_steps.  The
+    reader trains in fp32.  ``graph``: only False, as for StaticTrainStep."""
+
+    name = "StaticPillarsTrainStep"
+
+    def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
+                 max_gt=None, timesteps=None, graph=False):
+        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph)
+        if not 1 <= self.B <= 16:
+            raise ValueError("StaticPillarsTrainStep: the pillar reader takes 1 to 16 clouds per batch (got %d)" % self.B)
+
+    def _check_model(self, model):
+        from .detectors import PointPillars
+
+        if not isinstance(model, PointPillars):
+            raise NotImplementedError("StaticPillarsTrainStep: %s is not a PointPillars detector (a VoxelNet trains through "
+                                      "StaticTrainStep)" % type(model).__name__)
+        if getattr(model.bbox_head, "dcn_head", False):
+            raise NotImplementedError("StaticPillarsTrainStep: a dcn_head CenterHead is not covered (dcn_head=True); train it through "
+                                      "train_steps")
+
+    def _forward(self, clouds, counts, example, static):
+        return self.model.forward_points_train(clouds, self.voxel_cfg, example, counts=counts, static=static, bev_map=self.bev)
+
+    def warm_up(self, batches):
+        """Eager steps on the host-count path (forward_points_train(static=False)) over representative batches: lets the dense convolutions
+        pick their kernels and fixes the optimiser's gradient set and pointer table.  The model, the optimiser and the iteration count
+        are restored afterwards."""
+        self._warm(batches)
+
+    def __call__(self, batch, check=True):
+        """One iteration on ``batch``.  ``check`` is accepted for StaticTrainStep's signature: nothing can overflow, nothing is read back."""
+        self._load(batch, self.iteration)
+        self.outputs, self.level_counts = self._run_static()
+        self.iteration += 1
+        return self.outputs
+
+    def overflowed(self, level_counts_host=None):
+        return False
+
+
 __all__ = ["FusedAdam", "OneCycle", "LRSchedulerStep", "annealing_cos", "parameter_groups", "parse_grad_clip", "build_one_cycle_optimizer",
-           "create_learning_rate_scheduler", "train_steps", "StaticTrainStep"]
+           "create_learning_rate_scheduler", "train_steps", "StaticTrainStep", "StaticPillarsTrainStep"]

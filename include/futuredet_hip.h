@@ -654,6 +654,41 @@ int fd_pillar_train_backward(const float *voxels, const int32_t *num_points, con
                              void *workspace, size_t workspace_bytes, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The same reader with its pillar counts in device memory (fd_pillars_grad.hip), for a training step that never waits for the
+ * device.  Purely additive: fd_abi_version() stays 8.  The same kernels as the pair above, which are their one-segment,
+ * host-count case.
+ *   The buffers hold n_seg segments (1 <= n_seg <= 16) of seg_stride rows: voxels [n_seg * seg_stride, P, ndim], num_points and
+ *   coors4 alike.  Segment b owns rows [b * seg_stride, b * seg_stride + cnt_b), cnt_b = clamp(seg_counts[b], 0, seg_stride),
+ *   seg_counts a device int32[n_seg].  Rows behind a count may hold anything: they are neither read nor used as an address.
+ *   The logical batch is the segments' live pillars in segment order, M = sum cnt_b pillars, N = M * P rows.
+ *   fd_pillar_train_forward_dev / _backward_dev: the SAME BITS (out's live rows, the four statistics, the six gradients) as
+ *                     fd_pillar_train_forward / _backward with m = M on those pillars in one contiguous buffer: pillars per block and
+ *                     the live blocks come from the device total, the launch is sized by the capacity.  out [n_seg * seg_stride, 64]
+ *                     is defined everywhere: rows behind a count are 0; dout has the same shape (its rows behind a count are not
+ *                     read).  N < 2 (the empty batch): out, the statistics and every gradient are 0.
+ *   fd_pillar_train_running_stats_dev: torch's BatchNorm rule for one layer, with n = P * sum cnt_b read on the device:
+ *                     num_batches_tracked (int64, may be NULL) += 1, running_mean <- (1 - momentum) running_mean + momentum mean,
+ *                     running_var <- (1 - momentum) running_var + momentum var n / (n - 1); evaluated in double precision, rounded
+ *                     once.  n < 2: nothing is written.
+ * workspace >= fd_pillar_train_workspace_bytes(n_seg * seg_stride, max_points): sized by the capacity.  No atomics, no allocation,
+ * no synchronisation; deterministic and capturable like the pair above.
+ * ------------------------------------------------------------------------------------------------- */
+int fd_pillar_train_forward_dev(const float *voxels, const int32_t *num_points, const int32_t *coors4, const int32_t *seg_counts, int n_seg,
+                                int64_t seg_stride, int max_points, int ndim, int with_distance, float vx, float vy, float x_offset,
+                                float y_offset, const float *w1, const float *gamma1, const float *beta1, int units1, float eps1,
+                                const float *w2, const float *gamma2, const float *beta2, int units2, float eps2, float *out, float *mean1,
+                                float *var1, float *mean2, float *var2, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_pillar_train_backward_dev(const float *voxels, const int32_t *num_points, const int32_t *coors4, const int32_t *seg_counts, int n_seg,
+                                 int64_t seg_stride, int max_points, int ndim, int with_distance, float vx, float vy, float x_offset,
+                                 float y_offset, const float *w1, const float *gamma1, const float *beta1, int units1, const float *w2,
+                                 const float *gamma2, const float *beta2, int units2, const float *dout, float *dw1, float *dgamma1,
+                                 float *dbeta1, float *dw2, float *dgamma2, float *dbeta2, void *workspace, size_t workspace_bytes,
+                                 fd_stream_t stream);
+int fd_pillar_train_running_stats_dev(const float *mean, const float *var, int channels, double momentum, const int32_t *seg_counts, int n_seg,
+                                      int64_t seg_stride, int max_points, float *running_mean, float *running_var,
+                                      int64_t *num_batches_tracked, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training: one optimiser step for a whole model (fd_optim.hip).  Purely additive: fd_abi_version() stays 8.  fp32.
  * Replaces, for the recipe of every shipped config (adam, fixed_wd, one_cycle, grad_clip max_norm / norm_type 2):
  *   the true weight decay of OptimWrapper.step, p.data.mul_(1 - wd * lr) on every parameter of both groups
