@@ -1641,6 +1641,61 @@ def levels_overflow(counts, caps, flag=None):
     return flag
 
 
+# ---- training: the global augmentation (fd_augment.hip) ---------------------------------------------------------------------------
+AUGMENT_RECORD_DOUBLES = ctypes.sizeof(_lib.AugmentRecord) // 8  # a record travels as 6 float64 words (48 bytes, 8-byte aligned)
+
+
+def _augment_records(rec, name, n):
+    rec = _dev(rec, name, torch.float64)
+    if rec.numel() != n * AUGMENT_RECORD_DOUBLES:
+        raise FutureDetHipError("%s must hold %d record(s) of %d float64 words (augment.GlobalAugment.record), got %s"
+                                % (name, n, AUGMENT_RECORD_DOUBLES, tuple(rec.shape)))
+    return rec
+
+
+def augment_points(src, rec, dst, perm=None, n_rows=None):
+    """fd_augment_points: dst[i] = A(src[perm[i]]) (perm None: src[i]) for the first ``n_rows`` (default: all) rows of src [n, 4 | 5] fp32;
+    dst [>= n_rows, ndim] is another buffer and keeps its rows at or past n_rows.  ``rec``: ONE sample's record on the device (float64
+    [6], a row of GlobalAugment.record's upload), ``perm``: int32 [>= n_rows] on the device.  One launch, no allocation, no
+    synchronisation.  Returns dst."""
+    src, dst = _dev(src, "src", torch.float32), _dev(dst, "dst", torch.float32)
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[1] not in (4, 5) or dst.shape[1] != src.shape[1]:
+        raise FutureDetHipError("augment_points: src and dst must be [n, 4] or [n, 5] rows of one width (got %s and %s)"
+                                % (tuple(src.shape), tuple(dst.shape)))
+    n = int(src.shape[0]) if n_rows is None else int(n_rows)
+    if not 0 <= n <= min(int(src.shape[0]), int(dst.shape[0])):
+        raise FutureDetHipError("augment_points: n_rows = %d does not fit src %s and dst %s" % (n, tuple(src.shape), tuple(dst.shape)))
+    if src.device != dst.device:
+        raise FutureDetHipError("augment_points: src and dst live on different devices")
+    rec = _augment_records(rec, "rec", 1)
+    if perm is not None:
+        perm = _dev(perm, "perm", torch.int32)
+        if perm.dim() != 1 or perm.numel() < n:
+            raise FutureDetHipError("augment_points: perm must be an int32 vector of at least n_rows = %d entries (got %s)" % (n, tuple(perm.shape)))
+    check(_lib.load().fd_augment_points(_p(src), n, int(src.shape[1]), _p(perm), _p(rec), _p(dst), _stream()), "fd_augment_points")
+    return dst
+
+
+def augment_boxes(boxes, counts, recs, out=None):
+    """fd_augment_boxes: out [B, T, n_max, 12] = the box rows below counts [B, T] (int32, device) transformed with recs [B] (float64
+    [B, 6]), the padding rows copied.  ``out`` None: a new tensor; ``out is boxes``: in place.  One launch, no synchronisation."""
+    boxes = _dev(boxes, "boxes", torch.float32)
+    if boxes.dim() != 4 or boxes.shape[3] != 12 or boxes.shape[0] < 1 or boxes.shape[1] < 1:
+        raise FutureDetHipError("augment_boxes: boxes must be [B, T, n_max, 12] (got %s)" % (tuple(boxes.shape),))
+    B, T, n_max = (int(v) for v in boxes.shape[:3])
+    counts = _dev(counts, "counts", torch.int32)
+    if tuple(counts.shape) != (B, T):
+        raise FutureDetHipError("augment_boxes: counts must be int32 [%d, %d] (got %s)" % (B, T, tuple(counts.shape)))
+    recs = _augment_records(recs, "recs", B)
+    if out is None:
+        out = torch.empty_like(boxes)
+    out = _dev(out, "out", torch.float32)
+    if tuple(out.shape) != tuple(boxes.shape) or out.device != boxes.device:
+        raise FutureDetHipError("augment_boxes: out %s does not match boxes %s" % (tuple(out.shape), tuple(boxes.shape)))
+    check(_lib.load().fd_augment_boxes(_p(boxes), _p(counts), _p(recs), _p(out), B, T, n_max, _stream()), "fd_augment_boxes")
+    return out
+
+
 # ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------
 LOSS_MAPS = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")  # fd_loss_task.maps / d_maps, in this order
 

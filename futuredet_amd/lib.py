@@ -76,6 +76,11 @@ class DenseBnNhwcGroup(ctypes.Structure):  # struct fd_dense_bn_nhwc_group
                 ("c", c_int), ("eps", c_float), ("momentum", ctypes.c_double)]
 
 
+class AugmentRecord(ctypes.Structure):  # struct fd_augment_record
+    _fields_ = [("flip_a", ctypes.c_int32), ("flip_b", ctypes.c_int32), ("c", c_float), ("s", c_float), ("rot", c_float), ("scale", c_float),
+                ("tx", ctypes.c_double), ("ty", ctypes.c_double), ("tz", ctypes.c_double)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -217,6 +222,8 @@ SIGNATURES = {
     "fd_rows_colsum_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "fd_rows_colsum": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fd_levels_overflow": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "fd_augment_points": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fd_augment_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fd_loss_chunk": (c_int, []),
     "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),

@@ -351,7 +351,8 @@ class _StaticTrainBase(object):
         """the device flag that turns this iteration's optimiser step into a no-op, or None"""
         return None
 
-    def _init_common(self, model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph):
+    def _init_common(self, model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
+                     augment=None):
         name = self.name
         self._check_model(model)
         head = model.bbox_head
@@ -380,6 +381,9 @@ class _StaticTrainBase(object):
         self.bev = torch.zeros((B, 6, assigner.H, assigner.W), dtype=torch.float32, device=dev) if getattr(head, "bev_map", False) else None
         self.targets = assigner.outputs(B, T, dev)
         self.hyper = torch.zeros((len(hip_ops.HYPER_FIELDS),), dtype=torch.float64, device=dev)
+        # augment (augment.GlobalAugment or None): the records of fd_augment_points / fd_augment_boxes, one per cloud, and the last draw
+        self.augment, self.last_aug_params = augment, None
+        self.aug_rec = torch.zeros((B, hip_ops.AUGMENT_RECORD_DOUBLES), dtype=torch.float64, device=dev) if augment is not None else None
         self._ring, self._slot = None, 0
         self.iteration = 0
         self.outputs, self.level_counts = None, None
@@ -392,9 +396,12 @@ class _StaticTrainBase(object):
 
     # -- inputs
     def _pinned(self):
-        """a slot of the ring of pinned staging buffers (cloud counts, the six scalars), free again once its last copy has run"""
+        """a slot of the ring of pinned staging buffers (cloud counts, the six scalars, the event of its last copy, the augmentation
+        records), free again once its last copy has run"""
         if self._ring is None:
-            self._ring = [[torch.empty((self.B,), dtype=torch.int32).pin_memory(), torch.empty((6,), dtype=torch.float64).pin_memory(), None]
+            self._ring = [[torch.empty((self.B,), dtype=torch.int32).pin_memory(), torch.empty((6,), dtype=torch.float64).pin_memory(), None,
+                           torch.empty((self.B, hip_ops.AUGMENT_RECORD_DOUBLES), dtype=torch.float64).pin_memory()
+                           if self.augment is not None else None]
                           for _ in range(8)]
         slot = self._ring[self._slot % len(self._ring)]
         self._slot += 1
@@ -402,10 +409,28 @@ class _StaticTrainBase(object):
             slot[2].synchronize()  # (only when the stream is eight steps behind the host)
         return slot
 
+    def _aug_params(self, batch):
+        """this batch's augmentation parameters [B, 7]: batch["aug_params"], else a draw (not for a bev_map head, whose map must have
+        been warped with the same parameters by whoever made the batch)"""
+        from .augment import PARAM_FIELDS
+
+        params = batch.get("aug_params")
+        if params is None:
+            if self.bev is not None:
+                raise ValueError("%s: augment with a bev_map head needs batch[\"aug_params\"] [%d, %d] and a \"bev_map\" already warped "
+                                 "with them (the map warp, get_mask, is not built)" % (self.name, self.B, len(PARAM_FIELDS)))
+            params = self.augment.draw(self.B)
+        params = np.asarray(params, np.float64)
+        if params.shape != (self.B, len(PARAM_FIELDS)):
+            raise ValueError("aug_params %s: expected [%d, %d] (%s)" % (params.shape, self.B, len(PARAM_FIELDS), ", ".join(PARAM_FIELDS)))
+        return params
+
     def _load(self, batch, iteration):
         clouds = batch["clouds"]
         if len(clouds) != self.B:
             raise ValueError("the step was built for batches of %d clouds, got %d" % (self.B, len(clouds)))
+        aug = self.augment
+        params = self._aug_params(batch) if aug is not None else None  # (drawn or refused before anything of the step changes)
         if self.bev is not None:
             bev = batch.get("bev_map")
             if bev is None:
@@ -418,11 +443,18 @@ class _StaticTrainBase(object):
         slot = self._pinned()
         counts_host, hyper_host = slot[0], slot[1]
         hyper_host.numpy()[:] = self.optimizer.hyper_values(self.grad_clip)
+        if aug is not None:
+            slot[3].numpy()[:] = aug.record(params).view(np.float64).reshape(self.B, -1)
+            self.aug_rec.copy_(slot[3], non_blocking=True)
+            self.last_aug_params = params
         for b, c in enumerate(clouds):
             n = int(c.shape[0])
             if n > self.capacity or c.shape[1] != self.ndim:
                 raise ValueError("cloud of %d x %d rows does not fit the step's %d x %d buffer" % (n, c.shape[1], self.capacity, self.ndim))
-            self.points[b, :n].copy_(c, non_blocking=True)
+            if aug is None:
+                self.points[b, :n].copy_(c, non_blocking=True)
+            else:  # the shuffle and the transforms, straight from the batch's tensor
+                hip_ops.augment_points(c, self.aug_rec[b], self.points[b], perm=aug.permutation(n, self.device), n_rows=n)
             counts_host[b] = n
         self.counts.copy_(counts_host, non_blocking=True)
         self.hyper.copy_(hyper_host, non_blocking=True)
@@ -432,7 +464,12 @@ class _StaticTrainBase(object):
         n = int(boxes.shape[2])
         if tuple(boxes.shape[:2]) != (self.B, self.T) or n > self.max_gt or boxes.shape[3] != 12:
             raise ValueError("gt_boxes %s do not fit the step's [%d, %d, <= %d, 12] buffer" % (tuple(boxes.shape), self.B, self.T, self.max_gt))
-        self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
+        if aug is not None and n == self.max_gt and boxes.is_contiguous():
+            hip_ops.augment_boxes(boxes, gcounts, self.aug_rec, out=self.gt_boxes)
+        else:
+            self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
+            if aug is not None:  # narrower than the buffer: in place, the counts never reach past column n
+                hip_ops.augment_boxes(self.gt_boxes, gcounts, self.aug_rec, out=self.gt_boxes)
         self.gt_counts.copy_(gcounts, non_blocking=True)
         self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
         if self.gt_trajectory is not None:
@@ -527,6 +564,12 @@ class StaticTrainStep(_StaticTrainBase):
     asynchronous; ask ``overflowed()`` later.  What an overflowed step leaves behind: the BatchNorm running statistics (and
     num_batches_tracked) were updated once by its forward pass, on a truncated but valid batch, before the re-run updates them again.
 
+    ``augment`` (an augment.GlobalAugment; None = none, today's launches): the step draws one set of parameters per cloud (or takes
+    batch["aug_params"] [B, 7]), keeps them in ``last_aug_params``, uploads their records through the staging ring, and loads the
+    batch through fd_augment_points -- one launch per cloud, shuffle and transforms, in place of the copy -- and one fd_augment_boxes.
+    The warm-up and the overflow re-run read the static buffers, so they see the augmented batch once.  With a bev_map head the map
+    warp is not built: the batch must carry ``aug_params`` and a ``bev_map`` already warped with them, else ValueError.
+
     ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
     device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward
     included -- crashed the HIP runtime when the capture was ended (torch 2.10 on ROCm 7, MI355X; DESIGN.md "The sync-free training
@@ -535,8 +578,9 @@ class StaticTrainStep(_StaticTrainBase):
     name = "StaticTrainStep"
 
     def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
-                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False):
-        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph)
+                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False, augment=None):
+        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
+                          augment)
         self.row_caps_mode, self.headroom = row_caps, float(headroom)
         self.skip = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self.expected, self.caps, self.caps_dev = None, None, None
@@ -626,13 +670,14 @@ class StaticPillarsTrainStep(_StaticTrainBase):
     There are no row capacities and no overflow guard: the voxeliser caps the pillars of a cloud at max_voxel_num[0] and every buffer
     has that size, so ``overflowed()`` is False and ``check`` reads nothing back.  Needs bbox_head.fused_loss; a bev_map head takes
     batch["bev_map"]; neck / bbox_head train_dtype = torch.bfloat16 and the dense fused_bn switches work as in train_steps.  The
-    reader trains in fp32.  ``graph``: only False, as for StaticTrainStep."""
+    reader trains in fp32.  ``augment``: as for StaticTrainStep.  ``graph``: only False, as for StaticTrainStep."""
 
     name = "StaticPillarsTrainStep"
 
     def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
-                 max_gt=None, timesteps=None, graph=False):
-        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph)
+                 max_gt=None, timesteps=None, graph=False, augment=None):
+        self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
+                          augment)
         if not 1 <= self.B <= 16:
             raise ValueError("StaticPillarsTrainStep: the pillar reader takes 1 to 16 clouds per batch (got %d)" % self.B)
 

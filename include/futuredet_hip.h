@@ -770,6 +770,44 @@ int fd_rows_colsum(const void *x, int64_t n, const int32_t *n_dev, int C, int dt
 int fd_levels_overflow(const int32_t *counts, const int32_t *caps, int n_levels, int32_t *flag, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Training: the global augmentation of one sample (fd_augment.hip) -- the train-mode transforms of Preprocess
+ * (det3d/datasets/pipelines/preprocess.py:189-192, 201-203): prep.random_flip_both, prep.global_rotation, prep.global_scaling_v2 and
+ * prep.global_translate_ (det3d/core/sampler/preprocess.py:815-857, 776-799, 860-868, 967-992; the rotation itself is
+ * box_np_ops.rotation_points_single_angle, det3d/core/bbox/box_np_ops.py:182-204) and the fixed-seed point shuffle, as a permutation.
+ * Purely additive: fd_abi_version() stays 8.  One launch each, graph-capturable, no allocation, no workspace, no synchronisation.
+ * fd_augment_record: one sample's draw.  flip_a / flip_b: the reference's first / second flip (non-zero = on); c, s: the float64
+ *   cos / sin of the angle cast to fp32; rot, scale: the angle and the factor cast to fp32; tx, ty, tz: the float64 translation.
+ * The arithmetic A, every product and sum rounded once in fp32 unless said otherwise (NumPy 2 on fp32 arrays), in this order:
+ *   flip a   y = -y; boxes also columns 7 and 9, and columns 10, 11: a = -a + fl32(pi)
+ *   flip b   x = -x; boxes also columns 6 and 8, and columns 10, 11: a = -a + fl32(2 pi)
+ *   rotate   x' = x c + y s, y' = -(x s) + y c (z untouched); boxes: the column pairs (0, 1), (6, 7), (8, 9), and columns 10, 11 += rot.
+ *            (The reference rotates the pairs (6, 7) and (8, 9) through a float64 copy and its BLAS product fuses as it likes: its
+ *            rotated values lie within 4 ulp-sized steps of these, see tests/test_augment_host.py.)
+ *   scale    xyz of a point, columns 0..9 of a box, times scale
+ *   shift    fl32(double(v) + t) on x, y, z of points and boxes
+ * fd_augment_points: dst[i] = A(src[perm ? perm[i] : i]) for i < n_rows, rows of ndim (4 or 5) fp32; columns 3 and up pass through bit
+ *   for bit; dst rows at or past n_rows are not written.  perm: int32 [>= n_rows] in device memory, a permutation of 0..n_rows-1 (a
+ *   row whose index lies outside that range is left unwritten; nothing is read out of bounds), or NULL.  rec: ONE record in device
+ *   memory.  n_rows = 0 is a no-op.  16-byte accesses are used when src and dst are 16-byte aligned (ndim 5: and perm is NULL).
+ *   FD_EINVAL for: ndim not 4 or 5, n_rows outside [0, FD_AUGMENT_MAX_ROWS], a null or misaligned record, null or misaligned (4 bytes)
+ *   src / dst with n_rows > 0, src == dst or overlapping ranges.
+ * fd_augment_boxes: boxes / out [B, T, n_max, 12] fp32, 16-byte aligned; counts int32 [B, T] and recs [B] in device memory.  Row i of
+ *   (b, t) becomes A(row) with recs[b] when i < counts[b, t] and is copied unchanged otherwise.  out == boxes (in place) is allowed,
+ *   any other overlap is not.  n_max = 0 is a no-op.  FD_EINVAL for: B or T < 1, n_max < 0, more than FD_AUGMENT_MAX_ROWS rows, null
+ *   or misaligned pointers, partially overlapping boxes and out.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_AUGMENT_MAX_ROWS (1 << 28)
+typedef struct fd_augment_record {
+    int32_t flip_a, flip_b;
+    float c, s, rot, scale;
+    double tx, ty, tz;
+} fd_augment_record;
+int fd_augment_points(const float *src, int64_t n_rows, int ndim, const int32_t *perm, const fd_augment_record *rec, float *dst,
+                      fd_stream_t stream);
+int fd_augment_boxes(const float *boxes, const int32_t *counts, const fd_augment_record *recs, float *out, int B, int T, int n_max,
+                     fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
  * det3d/models/losses/centernet_loss.py as center_head.py:396-539 combines them, forward terms and the gradient of every head map.
  * Purely additive: fd_abi_version() stays 8.  fp32 maps, contiguous [B, channels, H, W].
