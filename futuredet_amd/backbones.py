@@ -242,6 +242,10 @@ class SpMiddleResNetFHD(nn.Module):
                             r = hip_ops.ranges_for(nbr, cp, cp)  # cached on the rulebook tensor; spconv_apply finds it there
                             if r[0] is not None:
                                 made.append(r[0])
+                        if dt == torch.float32 and nbr.shape[0] == 27 and dst_l.n > 0 and \
+                                hip_ops._lib.load().fd_spconv_plan_wanted(cp, cp, 0):
+                            # the level's chunk plan, for the row split its convolutions will ask for (cached on the rulebook tensor)
+                            made.append(hip_ops.plan_for(nbr, dst_l.n, *hip_ops.row_split(nbr, dst_l.n, cp, cp))[0])
                 for t in made:  # allocated on the side stream, consumed by kernels of the main stream
                     t.record_stream(main)
         x = feats0

@@ -264,9 +264,10 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
     return FD_OK;
 }
 
-extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
-                               const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
-                               const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats, fd_stream_t stream) {
+namespace {
+int spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu, const int32_t *nbr,
+                 int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out, const int32_t *n_out_dev, int64_t n_expected, int cin,
+                 int cout, int dtype, void *out_feats, fd_stream_t stream, const int32_t *plan, int64_t plan_stride) {
     FD_REQUIRE(K >= 1 && K <= fd::kSpconvMaxTaps, "fd_spconv_apply: K must be in [1,27]");
     FD_REQUIRE(dtype == 0 || dtype == 1, "fd_spconv_apply: dtype must be 0 (f32) or 1 (bf16)");
     FD_REQUIRE(n_out >= 0 && n_out <= nbr_stride && n_out < (1ll << 31), "fd_spconv_apply: n_out out of range");
@@ -275,7 +276,7 @@ extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *w
     if (n_out == 0) return FD_OK;  // an empty active set (empty cloud): nothing to compute, buffers may be null
     FD_REQUIRE(in_feats && wpacked && nbr && out_feats, "fd_spconv_apply: null argument");
     const fd::SpconvCall c{in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, (int)n_out, n_out_dev, n_expected,
-                           cin, cout, dtype, out_feats, fd::as_stream(stream)};
+                           cin, cout, dtype, out_feats, fd::as_stream(stream), plan, plan_stride};
     if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && cin == 16 && fd::tuning(fd::kTuneF32ResRG) >= 0) {
         // the 16-channel level: resident weights + register accumulators + empty-item skipping (fd_spconv_f32r.hip); "f32_res_rg" = -1
         // keeps the pair-compacting kernel for A/B runs
@@ -317,4 +318,27 @@ extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *w
             return FD_EINVAL;
     }
     return fd::check_launch("fd_spconv_apply");
+}
+}  // namespace
+
+extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
+                               const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
+                               const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats, fd_stream_t stream) {
+    return spconv_apply(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected, cin, cout,
+                        dtype, out_feats, stream, nullptr, 0);
+}
+
+// fd_spconv_apply with the rulebook's chunk plan (fd_spconv_plan_build): the kernels that take one (fd_spconv_plan_wanted) read their
+// chunks' compacted lists from it, every other kernel ignores it.  The same results bit for bit.
+extern "C" int fd_spconv_apply_plan(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
+                                    const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
+                                    const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats,
+                                    const int32_t *plan, int64_t plan_stride, fd_stream_t stream) {
+    if (plan) {
+        FD_REQUIRE(K == fd::kSpconvMaxTaps && dtype == 0 && cin == cout, "fd_spconv_apply_plan: a chunk plan belongs to an fp32 SubM layer (K = 27)");
+        FD_REQUIRE(plan_stride >= fd_spconv_plan_stride(n_out), "fd_spconv_apply_plan: plan_stride below fd_spconv_plan_stride(n_out)");
+        if (!fd_spconv_plan_wanted(cin, cout, dtype)) plan = nullptr;  // switched off, or a shape without the path: in-kernel compaction
+    }
+    return spconv_apply(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected, cin, cout,
+                        dtype, out_feats, stream, plan, plan_stride);
 }

@@ -32,7 +32,8 @@ constexpr int TM = 128, COUT = 32, TS = 4, WR = 1;
 constexpr sk::Layout L = sk::layout(TM, COUT, TS, 32);
 static_assert(((sk::kMaxTaps + TS - 1) / TS) * (TM / WR / 32) <= L.item_slot, "item list slot");
 
-template <int CIN, int DEPTH>
+// PLAN: nbr / nbr_stride are a chunk plan (fd_spconv_chunk.h) instead of the rulebook: the lists arrive compacted
+template <int CIN, int DEPTH, bool PLAN>
 __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ in, const float4 *__restrict__ wp, const float *__restrict__ bias,
                                                       const float *__restrict__ residual, int relu, const int *__restrict__ nbr, int64_t nbr_stride,
                                                       int K, int n_out, const int *__restrict__ n_out_dev, float *__restrict__ out, unsigned in_bytes,
@@ -52,7 +53,8 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
     if (r_begin >= r_end) return;
     sk::cut_chunks<TM>(r_begin, r_end, n_chunks, chunk_rows);
     int pre[sk::kSliceRegs<TM>];
-    sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, r_begin);
+    const int k_fetch = PLAN ? sk::kPlanRows : K;
+    sk::fetch_slice<TM>(pre, nbr, nbr_stride, k_fetch, r_begin);
 
     const int ln = lane & 31, lh = lane >> 5;
     const int ts = wave, wr = 0;
@@ -63,11 +65,15 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
         int row0, n_rows;
         if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
-        sk::stage_chunk<TM, COUT, TS, 32>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
+        if constexpr (PLAN) {
+            sk::stage_plan_chunk<TM, COUT, TS, 32>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, row0, n_rows);
+        } else {
+            sk::stage_chunk<TM, COUT, TS, 32>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
+            __syncthreads();
+            sk::compact_taps<TM, WR>(s_list, s_cnt, K);
+        }
         __syncthreads();
-        sk::compact_taps<TM, WR>(s_list, s_cnt, K);
-        __syncthreads();
-        if (chunk + 1 < n_chunks) sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, row0 + chunk_rows);  // the next chunk's slice travels while this chunk computes
+        if (chunk + 1 < n_chunks) sk::fetch_slice<TM>(pre, nbr, nbr_stride, k_fetch, row0 + chunk_rows);  // the next chunk's slice travels while this chunk computes
         const int n_items = sk::build_items<TS, 32>(s_cnt, items, K, ts, wr);
 
         // software pipeline as in the v2 kernel: item code one iteration ahead of the list entry, the list entry one ahead
@@ -151,17 +157,17 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
     }
 }
 
-template <int CIN, int DEPTH>
+template <int CIN, int DEPTH, bool PLAN>
 int launch_c32(const fd::SpconvCall &c) {
     const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
     int n_ranges = c.n_ranges, rows_per = 0;
     if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its dynamic-LDS limit raised (> 64 KB)
-    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(spconv_f32_c32<CIN, DEPTH>), (size_t)L.bytes, lds_set)) return 0;
+    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(spconv_f32_c32<CIN, DEPTH, PLAN>), (size_t)L.bytes, lds_set)) return 0;
     // the 32x32x2 fragment layout ([K][CIN / 8][64 lanes] float4, see fd_spconv_pack_weight)
     const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).c32.offset;
-    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, c.stream, (const float *)c.in, (const float4 *)wp,
-                       c.bias, (const float *)c.residual, c.relu, c.nbr, c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
+    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH, PLAN>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, c.stream, (const float *)c.in, (const float4 *)wp,
+                       c.bias, (const float *)c.residual, c.relu, PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }
 
@@ -172,6 +178,6 @@ namespace fd {
 int spconv_f32_c32_dispatch(const SpconvCall &c) {
     if (c.cout != 32 || c.cin != 32) return 0;
     if (!sk::entries_fit(c.n_in, c.cin)) return 0;
-    return launch_c32<32, 3>(c);
+    return c.plan ? launch_c32<32, 3, true>(c) : launch_c32<32, 3, false>(c);
 }
 }  // namespace fd

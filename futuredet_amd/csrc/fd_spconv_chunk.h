@@ -5,6 +5,7 @@
 //     while a chunk's MFMAs run, the next chunk's rulebook slice is already on its way into registers;
 //   * the rulebook tile [K][TM] is staged in LDS and compacted IN PLACE per tap with wave ballots / prefix popcounts into lists
 //     of (input row << 8 | local output row) entries, tails filled with the padding entry;
+//     a kernel given the rulebook's chunk plan finds those lists ready-made in global memory and only stages them ("chunk plan" below);
 //   * accumulators for the whole chunk live in LDS: TS copies (one per tap split) of [TM + 1][COUT] fp32; row TM is a scratch
 //     row that absorbs the padding lanes so the accumulator traffic needs no exec masking; 16-byte slots are XOR-swizzled by the
 //     row so the 16 rows of a lane group land on distinct banks;
@@ -199,6 +200,46 @@ __device__ __forceinline__ void stage_chunk(const int (&pre)[kSliceRegs<TM>], in
     for (int i = 0; i < kSliceRegs<TM>; ++i) {
         const int t = tid + i * 256;
         if (t < K * TM) s_list[t] = in_chunk ? pre[i] : -1;
+    }
+    init_acc<TM, COUT, TS>(s_acc, bias, residual, row0, n_rows);
+    if (tid < ITEM) s_pad[tid] = pad_entry(TM);
+}
+
+// ------------------------------------------------------------------------------------------------------ chunk plan
+// A SubM rulebook is shared by the 4-5 convolutions of its level, and the compacted lists of a chunk depend on nothing but the
+// rulebook and the chunk boundaries.  The chunk plan (chunk_plan_kernel in fd_spconv_v2.hip, one launch per rulebook) holds them
+// ready-made in the rulebook's own shape, so that a kernel fetches a chunk's lists with the very code that fetches its rulebook slice:
+//   rows 0 .. 26 of int [kPlanRows][plan_stride]: entry i of tap k's list of the chunk that starts at output row row0 is
+//     plan[k][row0 + i], i < n_rows; entries past the tap's count are the padding entry (what compact_taps<128, 1> leaves in LDS);
+//   row 27: the chunk's 27 pair counts as bytes, in the 8 words from plan[27][row0] (chunks start at multiples of 8 rows and
+//     never share a block of 8: the equal-rows split cuts at multiples of 16, fd_spconv_ranges at multiples of 8).
+// 128-row chunks with one row set (WR = 1) only: the 32 -> 32, 64 -> 64 and 128 -> 128 layers.
+constexpr int kPlanRows = kMaxTaps + 1;
+constexpr int kPlanTM = 128;
+constexpr int kPlanCountWords = (kMaxTaps + 3) / 4;
+// host: words per plan row for n_out output rows (the count words of the last chunk end before n_out + 8)
+inline int64_t plan_stride_for(int64_t n_out) { return (n_out + 8 + 63) / 64 * 64; }
+
+// stage_chunk for a kernel that fetched its slice from the plan (fetch_slice with K = kPlanRows): the lists go to LDS as they are
+// (positions past the chunk's rows belong to the next chunk: padding), the counts are unpacked; no compaction pass follows.
+template <int TM, int COUT, int TS, int ITEM>
+__device__ __forceinline__ void stage_plan_chunk(const int (&pre)[kSliceRegs<TM>], int *s_list, unsigned char *s_cnt, int *s_pad, float *s_acc,
+                                                 const float *bias, const float *residual, int row0, int n_rows) {
+    const int tid = threadIdx.x;
+    static_assert(TM == kPlanTM && 256 % TM == 0, "the plan is cut for 128-row chunks");
+    static_assert(kSliceRegs<TM> * 256 >= kMaxTaps * TM + kPlanCountWords, "the count words ride in the slice's last register");
+    const bool in_chunk = tid % TM < n_rows;
+#pragma unroll
+    for (int i = 0; i < kSliceRegs<TM>; ++i) {
+        const int t = tid + i * 256;
+        if (t < kMaxTaps * TM) {
+            s_list[t] = in_chunk ? pre[i] : pad_entry(TM);
+        } else if (t < kMaxTaps * TM + kPlanCountWords) {
+            const int k0 = (t - kMaxTaps * TM) * 4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (k0 + q < kMaxTaps) s_cnt[(k0 + q) * 4] = (unsigned char)((unsigned)pre[i] >> (8 * q));
+        }
     }
     init_acc<TM, COUT, TS>(s_acc, bias, residual, row0, n_rows);
     if (tid < ITEM) s_pad[tid] = pad_entry(TM);

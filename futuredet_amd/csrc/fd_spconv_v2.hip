@@ -33,7 +33,7 @@
 // slice prefetch and staging, tile init, compaction, work list, epilogue -- is shared with the 32-pair kernel (fd_spconv_c32.hip)
 // and lives in fd_spconv_chunk.h.  This file owns the 16-pair unit of work (wave -> column slice / tap split / row set mapping,
 // gather, weight slice in registers and its in-place reload, the 16x16x4 MFMA loop with its scheduling barriers), its dispatch
-// table, the phase trace (FD_V2_TRACE) and the work-balanced ranges.
+// table, the phase trace (FD_V2_TRACE), the work-balanced ranges and the chunk plan of a shared rulebook (chunk_plan_kernel).
 #include "fd_spconv_chunk.h"
 
 namespace {
@@ -68,7 +68,8 @@ __device__ unsigned long long *g_trace;
 // there anyway (these layers run two workgroups per CU).  16 columns keep four row quarters: measured faster.
 constexpr int tap_splits(int cout) { return (cout == 32 || cout == 64) ? 2 : 1; }
 
-template <int CIN, int COUT, int TM, int DEPTH>
+// PLAN: nbr / nbr_stride are a chunk plan (fd_spconv_chunk.h) instead of the rulebook: the lists arrive compacted
+template <int CIN, int COUT, int TM, int DEPTH, bool PLAN>
 __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restrict__ in, const float4 *__restrict__ wp,
                                                           const float *__restrict__ bias, const float *__restrict__ residual, int relu,
                                                           const int *__restrict__ nbr, int64_t nbr_stride, int K, int n_out,
@@ -81,6 +82,7 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     constexpr int WR = 4 / (WC * TS);             // row splits
     constexpr int NACC = NBW;  // one accumulator chain per column block (dependent 16x16x4 MFMAs issue back to back at full rate)
     static_assert((TM == 128 || TM == 64) && TM / WR >= 16, "local row uses 8 bits (0..TM, TM = scratch row)");
+    static_assert(!PLAN || (TM == sk::kPlanTM && WR == 1), "the chunk plan holds the lists of 128-row chunks with one row set");
     constexpr int kPad = sk::pad_entry(TM);
     constexpr sk::Layout L = sk::layout(TM, COUT, TS, 16);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -97,7 +99,8 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     FD_T(0);
     sk::cut_chunks<TM>(r_begin, r_end, n_chunks, chunk_rows);
     int pre[sk::kSliceRegs<TM>];
-    sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, r_begin);
+    const int k_fetch = PLAN ? sk::kPlanRows : K;
+    sk::fetch_slice<TM>(pre, nbr, nbr_stride, k_fetch, r_begin);
 
     const int lrow = lane & 15, lq = lane >> 4;
     const int wc = wave % WC, wr = TS == 1 ? wave / WC : 0, ts = TS == 1 ? 0 : wave / WC;
@@ -110,14 +113,18 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
     int row0, n_rows;
     if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
-    sk::stage_chunk<TM, COUT, TS, 16>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
-    __syncthreads();
-    if (chunk == 0) FD_T(1);
-    sk::compact_taps<TM, WR>(s_list, s_cnt, K);
+    if constexpr (PLAN) {
+        sk::stage_plan_chunk<TM, COUT, TS, 16>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, row0, n_rows);
+    } else {
+        sk::stage_chunk<TM, COUT, TS, 16>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
+        __syncthreads();
+        if (chunk == 0) FD_T(1);
+        sk::compact_taps<TM, WR>(s_list, s_cnt, K);
+    }
     __syncthreads();
     if (chunk == 0) FD_T(2);
     // the next chunk's slice travels while this chunk computes
-    if (chunk + 1 < n_chunks) sk::fetch_slice<TM>(pre, nbr, nbr_stride, K, row0 + chunk_rows);
+    if (chunk + 1 < n_chunks) sk::fetch_slice<TM>(pre, nbr, nbr_stride, k_fetch, row0 + chunk_rows);
     const int n_items = sk::build_items<TS, 16>(s_cnt, items, K, ts, wr);
 
     // ring of DEPTH prefetched items.  Gathers are buffer loads with hardware bounds checking: a padding lane / a
@@ -278,18 +285,23 @@ inline size_t lds_request(int cin, int cout, int tm) {
     return (cin == 64 && cout == 64 && tm == 128 && lds < 56 * 1024) ? (size_t)56 * 1024 : lds;
 }
 
-template <int CIN, int COUT, int TM, int DEPTH>
+template <int CIN, int COUT, int TM, int DEPTH, bool PLAN = false>
 int launch_compact(const fd::SpconvCall &c) {
+    // the layers whose rulebook comes with a chunk plan: SubM at 32 channels and up (one row set per 128-row chunk)
+    if constexpr (!PLAN && CIN == COUT && COUT >= 32 && TM == sk::kPlanTM) {
+        if (c.plan) return launch_compact<CIN, COUT, TM, DEPTH, true>(c);
+    }
     const size_t lds_req = lds_request(CIN, COUT, TM);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its LDS limit raised
-    auto kern = spconv_f32_compact<CIN, COUT, TM, DEPTH>;
+    auto kern = spconv_f32_compact<CIN, COUT, TM, DEPTH, PLAN>;
     if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_req, lds_set)) return 0;
     const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
     int n_ranges = c.n_ranges, rows_per = 0;
     if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
     const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).base.offset;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_ranges), dim3(256), lds_req, c.stream, (const float *)c.in, (const float4 *)wp, c.bias,
-                       (const float *)c.residual, c.relu, c.nbr, c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
+                       (const float *)c.residual, c.relu, PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev,
+                       (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }
 
@@ -442,7 +454,88 @@ __global__ void __launch_bounds__(1024) range_split_kernel(const unsigned *__res
     }
 }
 
+// ------------------------------------------------------------------------------------------------------- chunk plan
+// The compacted lists of every (range, chunk) of a shared rulebook, written once (layout: fd_spconv_chunk.h).  Workgroup
+// (x, y) of a grid of n_ranges x kPlanSplit resolves range x exactly as the convolution's workgroup x does (the same
+// resolve_range / cut_chunks / chunk_span, the same grid width) and takes its chunks y, y + kPlanSplit, ...; wave w compacts
+// the taps w, w + 4, ... of a chunk straight from global memory with compact_taps' ballots: the same entries in the same order.
+// No LDS, no barrier, nothing shared between workgroups.  Bound: reads the 4 K N_out bytes of the rulebook once, writes 4 (K + 1) N_out.
+constexpr int kPlanSplit = 4;
+__global__ void __launch_bounds__(256) chunk_plan_kernel(const int *__restrict__ nbr, int64_t nbr_stride, int n_out, const int *__restrict__ n_out_dev,
+                                                         const int *__restrict__ ranges, int rows_per_range, int *__restrict__ plan, int64_t plan_stride) {
+    constexpr int TM = sk::kPlanTM, K = sk::kMaxTaps, NT = (K + 3) / 4, NH = TM / 64;
+    constexpr int kPad = sk::pad_entry(TM);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int r_begin, r_end, n_chunks, chunk_rows;
+    sk::resolve_range(n_out, n_out_dev, ranges, rows_per_range, r_begin, r_end);
+    if (r_begin < 0 || r_begin >= r_end) return;
+    sk::cut_chunks<TM>(r_begin, r_end, n_chunks, chunk_rows);
+    for (int chunk = blockIdx.y; chunk < n_chunks; chunk += kPlanSplit) {
+        int row0, n_rows;
+        if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
+        // all of the wave's loads first (one memory round trip per chunk), rows past the chunk's end as "no pair"
+        int v[NT][NH];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int k = wave + 4 * j < K ? wave + 4 * j : K - 1;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int r = h * 64 + lane;
+                const int rr = r < n_rows ? r : n_rows - 1;  // (clamped address, selected on use)
+                v[j][h] = nbr[(int64_t)k * nbr_stride + row0 + rr];
+                if (r >= n_rows) v[j][h] = -1;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            const int k = wave + 4 * j;
+            if (k >= K) break;
+            int *list = plan + (int64_t)k * plan_stride + row0;  // [n_rows]
+            int count = 0;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const unsigned long long m = __ballot(v[j][h] >= 0);
+                const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
+                if (v[j][h] >= 0) list[pos] = sk::pack_entry(v[j][h], h * 64 + lane);
+                count += __popcll(m);
+            }
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int p = h * 64 + lane;
+                if (p >= count && p < n_rows) list[p] = kPad;
+            }
+            if (lane == 0) reinterpret_cast<unsigned char *>(plan + (int64_t)K * plan_stride + row0)[k] = (unsigned char)count;
+        }
+    }
+}
+
 }  // namespace
+
+// ---- the chunk plan of a shared rulebook (see fd_spconv_chunk.h and chunk_plan_kernel)
+extern "C" int64_t fd_spconv_plan_stride(int64_t n_out) { return n_out < 0 ? 0 : sk::plan_stride_for(n_out); }
+extern "C" size_t fd_spconv_plan_bytes(int64_t n_out) { return n_out < 0 ? 0 : sizeof(int32_t) * (size_t)sk::kPlanRows * (size_t)sk::plan_stride_for(n_out); }
+
+// 1 when fd_spconv_apply_plan reads a plan for this layer shape: the fp32 SubM layers whose kernels cut 128-row chunks with one row
+// set.  "spconv_plan" = -1 switches the plan off for A/B runs.
+extern "C" int fd_spconv_plan_wanted(int cin, int cout, int dtype) {
+    if (dtype != 0 || cin != cout || fd::tuning(fd::kTuneSpconvV1) || fd::tuning(fd::kTuneSpconvPlan) < 0) return 0;
+    return cin == 32 || cin == 64 || cin == 128;
+}
+
+extern "C" int fd_spconv_plan_build(const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out, const int32_t *n_out_dev, const int32_t *ranges,
+                                    int n_ranges, int32_t *plan, int64_t plan_stride, fd_stream_t stream_) {
+    FD_REQUIRE(K == sk::kMaxTaps, "fd_spconv_plan_build: a chunk plan belongs to a SubM rulebook (K = 27)");
+    FD_REQUIRE(n_out >= 0 && n_out <= nbr_stride && n_out < (1ll << 31), "fd_spconv_plan_build: n_out out of range");
+    FD_REQUIRE(n_ranges >= 0 && (ranges == nullptr || n_ranges >= 1), "fd_spconv_plan_build: ranges needs n_ranges >= 1");
+    if (n_out == 0) return FD_OK;
+    FD_REQUIRE(nbr && plan, "fd_spconv_plan_build: null argument");
+    FD_REQUIRE(plan_stride >= sk::plan_stride_for(n_out), "fd_spconv_plan_build: plan_stride below fd_spconv_plan_stride(n_out)");
+    int rows_per = 0;  // the split of the convolution launches (launch_compact / launch_c32)
+    if (!ranges) sk::equal_rows_split((int)n_out, sk::kPlanTM, n_out_dev != nullptr, n_ranges, rows_per);
+    hipLaunchKernelGGL(chunk_plan_kernel, dim3((unsigned)n_ranges, kPlanSplit), dim3(256), 0, fd::as_stream(stream_), nbr, nbr_stride, (int)n_out,
+                       n_out_dev, ranges, rows_per, plan, plan_stride);
+    return fd::check_launch("fd_spconv_plan_build");
+}
 
 #ifdef FD_V2_TRACE
 extern "C" int fd_debug_set_trace(void *p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &p, sizeof(p)) == hipSuccess ? 0 : -1; }

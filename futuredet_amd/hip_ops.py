@@ -325,6 +325,39 @@ def ranges_for(nbr, cin, cout):
     return nbr.ranges
 
 
+def row_split(nbr, n_out, cin, cout, balanced=None):
+    """(ranges, n_ranges) of an fp32 launch: the kernel walks row ranges.  The MFMA-bound SubM layers (Cout >= 64; their rulebook is
+    shared by the 4-5 convolutions of a level) get equal-WORK ranges from fd_spconv_ranges; narrow layers and strided convolutions
+    (rulebook used once) take equal row counts -- see fd_spconv_num_ranges for the measurements."""
+    L = _lib.load()
+    if balanced is None:
+        balanced = nbr.shape[0] == 27 and cin == cout and bool(L.fd_spconv_wants_balanced_ranges(cin, cout, 0))
+    if balanced == "tiles":      # one 128-row tile per workgroup (tuning comparisons)
+        return None, 0
+    if balanced:
+        return ranges_for(nbr, cin, cout)
+    return None, int(L.fd_spconv_num_ranges(getattr(nbr, "n_expected", 0) or n_out, cin, cout, 0))
+
+
+def plan_for(nbr, n_out, ranges, n_ranges):
+    """Chunk plan of a SubM rulebook (fd_spconv_plan_build): the compacted pair lists of every 128-row chunk, written once per
+    rulebook and row split and shared by the convolutions that reuse the rulebook.  Sized by the rulebook's row capacity, no host
+    read.  Returns (plan int32[28, stride], stride)."""
+    key = (ranges.data_ptr() if ranges is not None else 0, int(n_ranges), int(n_out))
+    plans = getattr(nbr, "plans", None)
+    if plans is None:
+        plans = nbr.plans = {}
+    if key not in plans:
+        L = _lib.load()
+        K, nstride = nbr.shape
+        pstride = int(L.fd_spconv_plan_stride(n_out))
+        plan = torch.empty((28, pstride), dtype=torch.int32, device=nbr.device)
+        check(L.fd_spconv_plan_build(_p(nbr), nstride, K, n_out, _p(getattr(nbr, "n_dev", None)), _p(ranges), int(n_ranges), _p(plan), pstride,
+                                     _stream()), "fd_spconv_plan_build")
+        plans[key] = (plan, pstride, ranges)  # (the range table stays alive with the plan cut for it)
+    return plans[key][:2]
+
+
 def rows_permute(src, row_of, c_dst, dtype=torch.float32, n_rows=None, n_dev=None):
     L = _lib.load()
     src = _dev(src, "src", torch.float32)
@@ -460,7 +493,7 @@ def dense_gather(grad, index, c):
     return feats
 
 
-def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=False, out=None, balanced=None):
+def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=False, out=None, balanced=None, plan=None):
     L = _lib.load()
     feats = _dev(feats, "feats")
     dt = _DT[feats.dtype]
@@ -471,20 +504,19 @@ def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=Fal
         out = torch.empty((max(n_out, 1), out_cols), dtype=out_dtype, device=feats.device)[:n_out]
     if residual is not None:
         _dev(residual, "residual", out_dtype)
-    # fp32: the kernel walks row ranges.  The MFMA-bound SubM layers (Cout >= 64; their rulebook is shared by the 4-5
-    # convolutions of a level) get equal-WORK ranges from fd_spconv_ranges; narrow layers and strided convolutions (rulebook
-    # used once) take equal row counts -- see fd_spconv_num_ranges for the measurements.
-    ranges, n_ranges = None, 0
     n_dev, n_expected = getattr(nbr, "n_dev", None), getattr(nbr, "n_expected", 0)  # static index: n_out is a capacity
-    if dt == 0 and n_out > 0:
-        if balanced is None:
-            balanced = K == 27 and cin == cout and bool(L.fd_spconv_wants_balanced_ranges(cin, cout, 0))
-        if balanced == "tiles":      # one 128-row tile per workgroup (tuning comparisons)
-            n_ranges = 0
-        elif balanced:
-            ranges, n_ranges = ranges_for(nbr, cin, cout)
-        else:
-            n_ranges = int(L.fd_spconv_num_ranges(n_expected or n_out, cin, cout, 0))
+    ranges, n_ranges = row_split(nbr, n_out, cin, cout, balanced) if dt == 0 and n_out > 0 else (None, 0)
+    # fp32 SubM layers from 32 channels up: the rulebook's chunk plan (plan_for), cut for this launch's row split and shared by the
+    # convolutions of the level.  ``plan=False`` (the training path) keeps the in-kernel compaction; the results are the same bits.
+    if plan is None:
+        plan = dt == 0 and n_out > 0 and K == 27 and cin == cout and bool(L.fd_spconv_plan_wanted(cin, cout, 0))
+    if plan:
+        plan_t, pstride = plan_for(_dev(nbr, "nbr", torch.int32), n_out, ranges, n_ranges)
+        check(L.fd_spconv_apply_plan(_p(feats), feats.shape[0], _p(_dev(wpacked, "wpacked")), _p(bias), _p(residual), int(bool(relu)),
+                                     _p(nbr), nstride, _p(ranges), n_ranges, K, n_out, _p(n_dev), int(n_expected or 0),
+                                     cin, cout, dt, _p(out), _p(plan_t), pstride, _stream()),
+              "fd_spconv_apply_plan")
+        return out
     check(L.fd_spconv_apply(_p(feats), feats.shape[0], _p(_dev(wpacked, "wpacked")), _p(bias), _p(residual), int(bool(relu)),
                             _p(_dev(nbr, "nbr", torch.int32)), nstride, _p(ranges), n_ranges, K, n_out, _p(n_dev), int(n_expected or 0),
                             cin, cout, dt, _p(out), _stream()),

@@ -107,6 +107,12 @@ SIGNATURES = {
     "fd_spconv_wants_balanced_ranges": (c_int, [c_int, c_int, c_int]),
     "fd_spconv_ranges_workspace_bytes": (c_size_t, [c_i64]),
     "fd_spconv_ranges": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_spconv_plan_stride": (c_i64, [c_i64]),
+    "fd_spconv_plan_bytes": (c_size_t, [c_i64]),
+    "fd_spconv_plan_wanted": (c_int, [c_int, c_int, c_int]),
+    "fd_spconv_plan_build": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    "fd_spconv_apply_plan": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_i64,
+                                     c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     "fd_densify": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_i64,
                            c_i64, c_i64, c_i64, c_i64, c_void_p]),
     "fd_conv2d_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -147,7 +147,7 @@ class _SparseConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, bias, nbr, n_out, subm):
         wpk = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_PLAIN, feats.dtype)
-        out = hip_ops.spconv_apply(feats, wpk, bias, nbr, n_out, weight.shape[2])
+        out = hip_ops.spconv_apply(feats, wpk, bias, nbr, n_out, weight.shape[2], plan=False)
         ctx.save_for_backward(feats, weight)
         ctx.nbr, ctx.n_out, ctx.subm, ctx.has_bias = nbr, n_out, subm, bias is not None
         return out
@@ -163,7 +163,7 @@ class _SparseConvFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if ctx.subm:  # the SubM table is symmetric: nbr[k][o] = i <=> nbr[K-1-k][i] = o
                 wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_FLIPPED_TRANSPOSED, dt)
-                dx = hip_ops.spconv_apply(dy, wt, None, nbr, n_in, cin_p)
+                dx = hip_ops.spconv_apply(dy, wt, None, nbr, n_in, cin_p, plan=False)
             else:
                 inv = getattr(nbr, "inv", None)  # cached with the rulebook (indice_key)
                 if inv is None:
@@ -171,7 +171,7 @@ class _SparseConvFunction(torch.autograd.Function):
                     if getattr(nbr, "n_in_dev", None) is not None:  # static indexes: dX has the INPUT level's rows, n_in is their capacity
                         inv.n_dev, inv.n_expected = nbr.n_in_dev, nbr.n_in_expected
                 wt = hip_ops.pack_spconv_weight_device(weight, hip_ops.PACK_TRANSPOSED, dt)
-                dx = hip_ops.spconv_apply(dy, wt, None, inv, n_in, cin_p)
+                dx = hip_ops.spconv_apply(dy, wt, None, inv, n_in, cin_p, plan=False)
         if ctx.needs_input_grad[1]:
             dw = hip_ops.spconv_wgrad(feats, dy, nbr, n_out)
         if ctx.has_bias and ctx.needs_input_grad[2]:

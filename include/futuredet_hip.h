@@ -38,7 +38,7 @@ const char *fd_last_error(void);
  * the 16-pair compacting kernel instead of the 32-pair one), "v2_ranges_per_cu" (row ranges per compute unit of the compacting
  * kernels), "f32_res_rg" (-1: 16-channel fp32 layers on the pair-compacting kernel instead of the resident-weights one; 2: two row
  * groups per wave; 32: 16 -> 32 on it as well), "f32_res_nw" (1: that kernel on XCD-contiguous tile chunks instead of interleaved
- * tiles), "bf16_gp" (-1: bf16 on the register kernel), "bf16_rg" / "bf16_depth" (row groups per wave / gather-ring depth of the bf16
+ * tiles), "spconv_plan" (-1: fd_spconv_apply_plan ignores the chunk plan), "bf16_gp" (-1: bf16 on the register kernel), "bf16_rg" / "bf16_depth" (row groups per wave / gather-ring depth of the bf16
  * kernels), "bf16_win" (-1: the 64 -> 64 / 128 -> 128 bf16 layers on the RING / RESIDENT kernels instead of the LDS-window
  * kernel), "bf16_nw" (1: RESIDENT bf16 kernels walk XCD-contiguous tile chunks instead of tiles interleaved over the grid),
  * "conv_nt" (output channels per workgroup of the bf16 dense conv: 64 | 32), "conv_strip" (1: stride-1 bf16 dense layers on strips
@@ -154,6 +154,23 @@ int fd_spconv_wants_balanced_ranges(int cin, int cout, int dtype); /* 1: use fd_
 size_t fd_spconv_ranges_workspace_bytes(int64_t n_out);
 int fd_spconv_ranges(const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out, const int32_t *n_out_dev, int n_ranges,
                      int32_t *ranges /*[n_ranges+1]*/, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+/* Chunk plan of a SubM rulebook (K = 27; fp32; no reference counterpart).  The fp32 kernels compact every 128-row chunk of the
+ * rulebook into per-tap pair lists before they compute; the lists depend only on the rulebook and on the row ranges, so the 4-5
+ * convolutions that share an indice_key can share them.  fd_spconv_plan_build writes them once, in one launch, with no host read
+ * (graph-capturable): plan is int32 [28, plan_stride], plan_stride >= fd_spconv_plan_stride(n_out), fd_spconv_plan_bytes(n_out) bytes
+ * at that stride; n_out may be a capacity (n_out_dev as in fd_spconv_apply: rows past the device's count get no entry and are never
+ * read).  fd_spconv_apply_plan is fd_spconv_apply with that plan: it must be given the n_out, n_out_dev, ranges and n_ranges the plan
+ * was built with (range boundaries multiples of 8 rows, as fd_spconv_ranges makes them).  Layer shapes for which
+ * fd_spconv_plan_wanted is 0 (and plan == NULL) run exactly fd_spconv_apply; results are bit-identical either way. */
+int64_t fd_spconv_plan_stride(int64_t n_out);
+size_t fd_spconv_plan_bytes(int64_t n_out);
+int fd_spconv_plan_wanted(int cin, int cout, int dtype);
+int fd_spconv_plan_build(const int32_t *nbr, int64_t nbr_stride, int K, int64_t n_out, const int32_t *n_out_dev, const int32_t *ranges,
+                         int n_ranges, int32_t *plan, int64_t plan_stride, fd_stream_t stream);
+int fd_spconv_apply_plan(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
+                         const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
+                         const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats, const int32_t *plan,
+                         int64_t plan_stride, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Densify.  Replaces SparseConvTensor.dense() + view (scn.py:165-168): out[b, c*D + d, y, x] = feats[row, c].

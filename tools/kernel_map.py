@@ -7,7 +7,7 @@ import sys
 STAGES = [
     ("sweep assembly", ("sweep_count", "sweep_scan", "sweep_write")),
     ("voxelizer + mean reader", ("vox_",)),
-    ("index pyramid + rulebooks", ("idx_", "rows_place", "rows_permute", "rulebook_kernel", "block_work_kernel", "range_split_kernel")),
+    ("index pyramid + rulebooks", ("idx_", "rows_place", "rows_permute", "rulebook_kernel", "block_work_kernel", "range_split_kernel", "chunk_plan_kernel")),
     ("sparse conv 128->128", ("spconv_f32_compact<128, 128", "spconv_bf16_win<128, 128", "spconv_bf16_ws<128, 128")),
     ("sparse conv 64->64", ("spconv_f32_compact<64, 64", "spconv_bf16_win<64, 64")),
     ("sparse conv 32->32", ("spconv_f32_c32<32", "spconv_bf16_ws<32, 32")),
