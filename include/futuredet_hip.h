@@ -904,7 +904,7 @@ int fd_centerhead_loss_backward(const fd_loss_cfg *cfg, const fd_loss_task *task
 
 /* ---------------------------------------------------------------------------------------------------
  * Training: BatchNorm1d on batch statistics over the rows of a sparse feature matrix, fused with the ReLU and the residual add that
- * follow it in SpMiddleResNetFHD (fd_sparse_bn.hip).  Purely additive: fd_abi_version() stays 8.
+ * follow it in SpMiddleResNetFHD (fd_sparse_bn.hip; the kernels are those of fd_row_bn.h).  Purely additive: fd_abi_version() stays 8.
  * fp32, row-major contiguous x [n, C]; C a multiple of 16 in [16, 128]; relu 0 or 1; residual [n, C] or NULL.
  * The _bf16 entry points take bf16 rows (the bits, as uint16_t) for x, residual, y, dy, dx and d_residual; gamma, beta, saved, the
  * running statistics, dgamma, dbeta and the workspace stay fp32 (one workspace size serves both).  A row is widened exactly on load
@@ -977,7 +977,7 @@ int fd_dense_bn_train_backward(const float *dy, const float *x, const float *y, 
 
 /* ---------------------------------------------------------------------------------------------------
  * Mixed-precision training: BatchNorm2d on batch statistics over a bf16 channels-last map of the dense half, fused with the ReLU that
- * follows it (fd_dense_bn_nhwc.hip).  Purely additive: fd_abi_version() stays 8.
+ * follows it (fd_dense_bn_nhwc.hip; the kernels are those of fd_row_bn.h).  Purely additive: fd_abi_version() stays 8.
  * The map is rows x [n = B H W, C], bf16 (the bits, as uint16_t), row-major contiguous; C a multiple of 32 in [32, 512]; n in [2, 2^30];
  * relu 0 or 1.  y, dy and dx are bf16 rows like x: a row is widened exactly on load and rounded once, to nearest even (a NaN stays a NaN),
  * on store.  saved [2, C], dgamma [C], dbeta [C], the parameters, the running statistics and the workspace are fp32.
@@ -989,7 +989,7 @@ int fd_dense_bn_train_backward(const float *dy, const float *x, const float *y, 
  *             running_var the same with the unbiased variance var n / (n - 1), num_batches_tracked (int64) += 1 -- all on the device.
  *   backward: g = dy where y > 0 (relu = 1; y is the forward's output) or dy;  dbeta = sum g;  dgamma = sum g x^,
  *             x^ = (x - mean) invstd;  dx = gamma invstd (g - dbeta / n - x^ dgamma / n).  Reads only gamma of a record.
- * Sums: the design of fd_sparse_bn.hip.  Rows are cut into chunks of fd_dense_bn_nhwc_chunk() (= FD_DENSE_BN_NHWC_CHUNK) rows;
+ * Sums: the design of fd_row_bn.h, shared with fd_sparse_bn_*.  Rows are cut into chunks of fd_dense_bn_nhwc_chunk() (= FD_DENSE_BN_NHWC_CHUNK) rows;
  * consecutive chunks form at most fd_dense_bn_nhwc_stat_groups() groups; a chunk's partial is centred at the chunk's own mean; partials are
  * combined in double, in a fixed order, with Chan's rule.  The element-wise passes cut the rows into at most
  * fd_dense_bn_nhwc_apply_blocks() blocks of whole chunks.  No atomics, and every boundary follows from (n, C): the same bits on every run.

@@ -1,5 +1,5 @@
-"""-m gpu: the fused training-mode BatchNorm2d (+ ReLU) on bf16 channels-last maps (futuredet_amd/csrc/fd_dense_bn_nhwc.hip,
-dense_bn.batch_norm2d_act_nhwc, RPN.fused_bn / CenterHead.fused_bn with train_dtype = torch.bfloat16) against the formulas in float64
+"""-m gpu: the fused training-mode BatchNorm2d (+ ReLU) on bf16 channels-last maps (futuredet_amd/csrc/fd_dense_bn_nhwc.hip over
+fd_row_bn.h, dense_bn.batch_norm2d_act_nhwc, RPN.fused_bn / CenterHead.fused_bn with train_dtype = torch.bfloat16) against the formulas in float64
 on the bf16-rounded x and dy.
 
 Inputs, references and gates are those of test_gpu_sparse_bn.py: fp32 results (saved, running statistics, dgamma, dbeta) within

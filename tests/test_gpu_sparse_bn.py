@@ -1,4 +1,4 @@
-"""-m gpu: the fused training-mode BatchNorm of the sparse backbone (futuredet_amd/csrc/fd_sparse_bn.hip, sparse.batch_norm_act,
+"""-m gpu: the fused training-mode BatchNorm of the sparse backbone (futuredet_amd/csrc/fd_sparse_bn.hip over fd_row_bn.h, sparse.batch_norm_act,
 SpMiddleResNetFHD.fused_bn) against the formulas in float64 on the same fp32 inputs.
 
 The backward reference is teacher-forced: it takes its ReLU mask from the kernel's own y (a y within rounding of 0 would otherwise flip

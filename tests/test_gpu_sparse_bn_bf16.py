@@ -1,5 +1,5 @@
-"""-m gpu: the bf16-row form of the fused training-mode BatchNorm of the sparse backbone (futuredet_amd/csrc/fd_sparse_bn.hip,
-sparse.batch_norm_act, SpMiddleResNetFHD.fused_bn with train_dtype = torch.bfloat16).
+"""-m gpu: the bf16-row form of the fused training-mode BatchNorm of the sparse backbone (futuredet_amd/csrc/fd_sparse_bn.hip over
+fd_row_bn.h, sparse.batch_norm_act, SpMiddleResNetFHD.fused_bn with train_dtype = torch.bfloat16).
 
 The bf16 kernels are the fp32 kernels with another load and store of a thread's four channels: a bf16 row is widened exactly on load and
 rounded to nearest even on store.  So test 1 asks for bits: statistics and parameter gradients equal to those of the fp32 entry points on

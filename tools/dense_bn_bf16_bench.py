@@ -1,6 +1,6 @@
 """Training-mode BatchNorm2d + ReLU on bf16 channels-last maps (mixed precision, train_dtype = torch.bfloat16): the fused kernels of
-fd_dense_bn_nhwc.hip (dense_bn.batch_norm2d_act_nhwc, fused_bn on) against the un-fused recipe they replace (bn(x.float()), ReLU and one
-rounding as separate passes, fused_bn off), both sides in one process, alternating inside one timing loop.
+fd_row_bn.h behind fd_dense_bn_nhwc.hip (dense_bn.batch_norm2d_act_nhwc, fused_bn on) against the un-fused recipe they replace
+(bn(x.float()), ReLU and one rounding as separate passes, fused_bn off), both sides in one process, alternating inside one timing loop.
 
 Every figure is device time between two events around forward + backward, the median of ``--iters`` samples after a warm-up, with
 the spread (min .. max) of each side.  The fused side counts as faster only where the gap between the medians exceeds the spread of the
@@ -45,7 +45,7 @@ B = 2
 SHAPES = [([128], 180, "RPN stage 1"), ([256], 180, "RPN deblocks"), ([256], 90, "RPN stage 2"), ([64], 180, "CenterHead shared_conv"),
           ([64] * 6, 180, "SepHead branches, grouped")]
 # bytes per element of the map that each kernel reads + writes (bf16 rows)
-KERNEL_BYTES = (("bn_nhwc_stats", 2), ("bn_nhwc_apply", 4), ("bn_nhwc_grad_sums", 6), ("bn_nhwc_grad_apply", 8))
+KERNEL_BYTES = (("row_bn_stats", 2), ("row_bn_apply", 4), ("row_bn_grad_sums", 6), ("row_bn_grad_apply", 8))
 
 
 def timed_each(fns, iters, warmup=3):

@@ -1,5 +1,5 @@
 """Training-mode BatchNorm of the sparse backbone at the bench cloud (forecast_n0's SpMiddleResNetFHD, 300k synthetic points, one sample):
-the fused kernels (sparse.batch_norm_act, fd_sparse_bn.hip) against the module chain they replace, in the same run.
+the fused kernels (sparse.batch_norm_act, fd_row_bn.h behind fd_sparse_bn.hip) against the module chain they replace, in the same run.
 
 Per backbone level, on features of the level's size: forward + backward of  relu(bn(x))  and  relu(bn(x) + identity)  -- fused, and as
 nn.BatchNorm1d / add / relu through autograd; each both issued from Python and as one captured graph (device time without launch
