@@ -198,11 +198,16 @@ class SpMiddleResNetFHD(nn.Module):
         stages = self._stages()
         rb_cache = {}
 
+        # fp32 sweep: the K = 27 layers of levels 1-3 run on chunk plans made straight from the index (hip_ops.IndexRulebook) and
+        # their dense tables are never built -- unless a profile hook asks for a launch's pair count, which is counted on the table
+        from_index = dt == torch.float32
+
         def rulebook(src, dst, conv):
             ks, st, pd = conv.geometry()
             key = (id(src), id(dst), tuple(ks), tuple(st), tuple(pd))
             if key not in rb_cache:
-                rb_cache[key] = src.rulebook(dst, ks, st, pd)
+                layer = (spconv.pad_channels(conv.in_channels), spconv.pad_channels(conv.out_channels)) if from_index else None
+                rb_cache[key] = src.rulebook(dst, ks, st, pd, fp32_layer=layer)
             return rb_cache[key]
 
         def run(conv, bn, x, src, dst, relu, residual=None):
@@ -213,10 +218,32 @@ class SpMiddleResNetFHD(nn.Module):
             if self.profile_hook is not None:
                 s = 4 if dt == torch.float32 else 2
                 K = nbr.shape[0]
-                pairs = lambda: int((nbr[:, : dst.n] >= 0).sum().item())  # noqa: E731
+                table = lambda: nbr.table() if isinstance(nbr, hip_ops.IndexRulebook) else nbr  # noqa: E731
+                pairs = lambda: int((table()[:, : dst.n] >= 0).sum().item())  # noqa: E731
                 return self.profile_hook("spconv_%dx%d_K%d" % (cin_p, cout_p, K),
                                          dict(s=s, K=K, cin=cin_p, cout=cout_p, n_in=src.n, n_out=dst.n, pairs=pairs), fn)
             return fn()
+
+        def index_plans():
+            """The chunk plans of the sweep's index rulebooks, ahead of their first use: one launch for those whose row split is known
+            up front (the strided layers, the 32-channel level), the equal-work range tables of the wide levels, one launch for their
+            plans -- the tables of a launch overlap their load chains.  Returns the tensors made (cached on the rulebooks)."""
+            groups = ([], [])  # (row split known up front, equal-work ranges first)
+            for lvl, (conv, bn, blocks, is_subm_in) in enumerate(stages):
+                if lvl == 0:
+                    continue
+                src_l, dst_l = (idx[lvl] if is_subm_in else idx[lvl - 1]), idx[lvl]
+                for s_l, cv in [(src_l, conv)] + [(dst_l, b.conv1) for b in blocks[:1]]:  # (a level's blocks share one rulebook)
+                    nbr = rulebook(s_l, dst_l, cv)
+                    if isinstance(nbr, hip_ops.IndexRulebook):
+                        ci, co = spconv.pad_channels(cv.in_channels), spconv.pad_channels(cv.out_channels)
+                        groups[int(ci == co and bool(hip_ops._lib.load().fd_spconv_wants_balanced_ranges(ci, co, 0)))].append((nbr, ci, co))
+            made = []
+            for group in groups:
+                splits = [(rb,) + tuple(hip_ops.row_split(rb, rb.n_out, ci, co)) for rb, ci, co in group]
+                made += [r for _, r, _ in splits if r is not None]
+                made += hip_ops.plans_from_index(splits)
+            return made
 
         main, side = None, None
         if fork and feats0.is_cuda:
@@ -232,9 +259,13 @@ class SpMiddleResNetFHD(nn.Module):
                     if lvl == 0:
                         continue
                     src_l, dst_l = (idx[lvl] if is_subm_in else idx[lvl - 1]), idx[lvl]
-                    made.append(rulebook(src_l, dst_l, conv))
+                    nbr = rulebook(src_l, dst_l, conv)
+                    if not isinstance(nbr, hip_ops.IndexRulebook):
+                        made.append(nbr)
                     for blk in blocks:
                         nbr = rulebook(dst_l, dst_l, blk.conv1)
+                        if isinstance(nbr, hip_ops.IndexRulebook):
+                            continue
                         made.append(nbr)
                         cp = spconv.pad_channels(blk.conv1.out_channels)
                         if dt == torch.float32 and nbr.shape[0] == 27 and \
@@ -246,8 +277,11 @@ class SpMiddleResNetFHD(nn.Module):
                                 hip_ops._lib.load().fd_spconv_plan_wanted(cp, cp, 0):
                             # the level's chunk plan, for the row split its convolutions will ask for (cached on the rulebook tensor)
                             made.append(hip_ops.plan_for(nbr, dst_l.n, *hip_ops.row_split(nbr, dst_l.n, cp, cp))[0])
+                made += index_plans()
                 for t in made:  # allocated on the side stream, consumed by kernels of the main stream
                     t.record_stream(main)
+        elif from_index:
+            index_plans()
         x = feats0
         levels = {}
         for lvl, (conv, bn, blocks, is_subm_in) in enumerate(stages):

@@ -274,7 +274,7 @@ int spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const 
     FD_REQUIRE(n_ranges >= 0 && (ranges == nullptr || n_ranges >= 1), "fd_spconv_apply: ranges needs n_ranges >= 1");
     if (n_expected <= 0 || n_expected > n_out) n_expected = n_out;  // only steers launch heuristics
     if (n_out == 0) return FD_OK;  // an empty active set (empty cloud): nothing to compute, buffers may be null
-    FD_REQUIRE(in_feats && wpacked && nbr && out_feats, "fd_spconv_apply: null argument");
+    FD_REQUIRE(in_feats && wpacked && (nbr || plan) && out_feats, "fd_spconv_apply: null argument");
     const fd::SpconvCall c{in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, (int)n_out, n_out_dev, n_expected,
                            cin, cout, dtype, out_feats, fd::as_stream(stream), plan, plan_stride};
     if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && cin == 16 && fd::tuning(fd::kTuneF32ResRG) >= 0) {
@@ -300,6 +300,11 @@ int spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const 
         if (fd::tuning(fd::kTuneBf16Win) >= 0 && subm_like && fd::spconv_bf16_win_dispatch(c)) return fd::check_launch("fd_spconv_apply(bf16 window)");
         // register accumulators + LDS-shared weights (fd_spconv_bf16.hip)
         if (fd::spconv_bf16_ws_dispatch(c)) return fd::check_launch("fd_spconv_apply(bf16 ws)");
+    }
+    if (!nbr) {  // (fd_spconv_apply_plan without a table: only the kernels above read a plan)
+        fd::set_error("fd_spconv_apply_plan: no kernel runs %d -> %d on %lld input rows from a chunk plan alone: pass the rulebook table", cin, cout,
+                      (long long)n_in);
+        return FD_EINVAL;
     }
     // what is left below: the register-resident output-stationary kernels of round 1 -- the path for feature matrices of 2 GB and
     // more (the kernels above address rows through 32-bit buffer offsets) and the A/B partner of the variant tests
@@ -330,14 +335,23 @@ extern "C" int fd_spconv_apply(const void *in_feats, int64_t n_in, const void *w
 
 // fd_spconv_apply with the rulebook's chunk plan (fd_spconv_plan_build): the kernels that take one (fd_spconv_plan_wanted) read their
 // chunks' compacted lists from it, every other kernel ignores it.  The same results bit for bit.
+// nbr == NULL: the plan came straight from the index (fd_spconv_plan_from_index) and there is no table; only for the shapes of
+// fd_spconv_index_plan_wanted, whose kernels read nothing else.
 extern "C" int fd_spconv_apply_plan(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
                                     const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
                                     const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats,
                                     const int32_t *plan, int64_t plan_stride, fd_stream_t stream) {
+    FD_REQUIRE(nbr || plan, "fd_spconv_apply_plan: nbr == NULL needs a chunk plan (fd_spconv_plan_from_index)");
     if (plan) {
-        FD_REQUIRE(K == fd::kSpconvMaxTaps && dtype == 0 && cin == cout, "fd_spconv_apply_plan: a chunk plan belongs to an fp32 SubM layer (K = 27)");
+        FD_REQUIRE(K == fd::kSpconvMaxTaps && dtype == 0, "fd_spconv_apply_plan: a chunk plan belongs to an fp32 layer of K = 27 taps");
+        FD_REQUIRE(nbr == nullptr || cin == cout, "fd_spconv_apply_plan: next to a rulebook table a chunk plan belongs to an fp32 SubM layer (K = 27)");
         FD_REQUIRE(plan_stride >= fd_spconv_plan_stride(n_out), "fd_spconv_apply_plan: plan_stride below fd_spconv_plan_stride(n_out)");
-        if (!fd_spconv_plan_wanted(cin, cout, dtype)) plan = nullptr;  // switched off, or a shape without the path: in-kernel compaction
+        if (!nbr) {
+            FD_REQUIRE(fd_spconv_index_plan_wanted(cin, cout, dtype),
+                       "fd_spconv_apply_plan: nbr == NULL, but no kernel runs this layer shape from a chunk plan alone (fd_spconv_index_plan_wanted)");
+        } else if (!fd_spconv_plan_wanted(cin, cout, dtype)) {
+            plan = nullptr;  // switched off, or a shape without the path: in-kernel compaction
+        }
     }
     return spconv_apply(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected, cin, cout,
                         dtype, out_feats, stream, plan, plan_stride);

@@ -93,19 +93,25 @@ __device__ __forceinline__ unsigned acc_slot_bytes(unsigned row, unsigned col) {
 // -------------------------------------------------------------------------------------------- row range and chunks
 // This workgroup's row range: an entry of the `ranges` table, or the equal-rows split (made here from the device's count when
 // there is one, see equal_rows_split).  The range may be empty.
-__device__ __forceinline__ void resolve_range(int n_out, const int *n_out_dev, const int *ranges, int rows_per_range,
-                                              int &r_begin, int &r_end) {
+// Range `block` of `n_blocks`: what resolve_range gives workgroup `block` of a launch that is n_blocks wide (the plan builder of
+// several tables in one launch, whose grid is as wide as its widest table, resolves each table's ranges with that table's width).
+__device__ __forceinline__ void resolve_range_of(int block, int n_blocks, int n_out, const int *n_out_dev, const int *ranges, int rows_per_range,
+                                                 int &r_begin, int &r_end) {
     if (n_out_dev) n_out = fd::device_count(n_out, n_out_dev);  // capacity launch (see fd_common.h)
     if (ranges) {
-        r_begin = ranges[blockIdx.x];
-        r_end = ranges[blockIdx.x + 1];
+        r_begin = ranges[block];
+        r_end = ranges[block + 1];
     } else {
-        if (n_out_dev) rows_per_range = (((n_out + (int)gridDim.x - 1) / (int)gridDim.x) + 15) & ~15;
-        const int64_t b = (int64_t)blockIdx.x * rows_per_range;
+        if (n_out_dev) rows_per_range = (((n_out + n_blocks - 1) / n_blocks) + 15) & ~15;
+        const int64_t b = (int64_t)block * rows_per_range;
         r_begin = (int)(b < n_out ? b : n_out);
         r_end = (int)(b + rows_per_range < n_out ? b + rows_per_range : n_out);
     }
     if (r_end > n_out) r_end = n_out;
+}
+__device__ __forceinline__ void resolve_range(int n_out, const int *n_out_dev, const int *ranges, int rows_per_range,
+                                              int &r_begin, int &r_end) {
+    resolve_range_of((int)blockIdx.x, (int)gridDim.x, n_out, n_out_dev, ranges, rows_per_range, r_begin, r_end);
 }
 // the range is cut into equal chunks of at most TM rows (multiples of 16)
 template <int TM>
@@ -213,7 +219,8 @@ __device__ __forceinline__ void stage_chunk(const int (&pre)[kSliceRegs<TM>], in
 //     plan[k][row0 + i], i < n_rows; entries past the tap's count are the padding entry (what compact_taps<128, 1> leaves in LDS);
 //   row 27: the chunk's 27 pair counts as bytes, in the 8 words from plan[27][row0] (chunks start at multiples of 8 rows and
 //     never share a block of 8: the equal-rows split cuts at multiples of 16, fd_spconv_ranges at multiples of 8).
-// 128-row chunks with one row set (WR = 1) only: the 32 -> 32, 64 -> 64 and 128 -> 128 layers.
+// 128-row chunks with one row set (WR = 1) only: the 32 -> 32, 64 -> 64 and 128 -> 128 layers, and the strided 16 -> 32, 32 -> 64 and
+// 64 -> 128 layers, whose plan comes straight from the index (index_plan_kernel) since nothing else reads their table.
 constexpr int kPlanRows = kMaxTaps + 1;
 constexpr int kPlanTM = 128;
 constexpr int kPlanCountWords = (kMaxTaps + 3) / 4;

@@ -33,7 +33,8 @@
 // slice prefetch and staging, tile init, compaction, work list, epilogue -- is shared with the 32-pair kernel (fd_spconv_c32.hip)
 // and lives in fd_spconv_chunk.h.  This file owns the 16-pair unit of work (wave -> column slice / tap split / row set mapping,
 // gather, weight slice in registers and its in-place reload, the 16x16x4 MFMA loop with its scheduling barriers), its dispatch
-// table, the phase trace (FD_V2_TRACE), the work-balanced ranges and the chunk plan of a shared rulebook (chunk_plan_kernel).
+// table, the phase trace (FD_V2_TRACE), the work-balanced ranges and the chunk plan of a shared rulebook (chunk_plan_kernel), and the
+// kernels that make plan and block works straight from the sparse index, without the table (index_plan_kernel, index_work_kernel).
 #include "fd_spconv_chunk.h"
 
 namespace {
@@ -287,8 +288,9 @@ inline size_t lds_request(int cin, int cout, int tm) {
 
 template <int CIN, int COUT, int TM, int DEPTH, bool PLAN = false>
 int launch_compact(const fd::SpconvCall &c) {
-    // the layers whose rulebook comes with a chunk plan: SubM at 32 channels and up (one row set per 128-row chunk)
-    if constexpr (!PLAN && CIN == COUT && COUT >= 32 && TM == sk::kPlanTM) {
+    // the layers that read a chunk plan: SubM at 32 channels and up, and the strided 16 -> 32, 32 -> 64, 64 -> 128 (one row set per
+    // 128-row chunk each)
+    if constexpr (!PLAN && ((CIN == COUT && COUT >= 32) || COUT == 2 * CIN) && TM == sk::kPlanTM) {
         if (c.plan) return launch_compact<CIN, COUT, TM, DEPTH, true>(c);
     }
     const size_t lds_req = lds_request(CIN, COUT, TM);
@@ -509,6 +511,137 @@ __global__ void __launch_bounds__(256) chunk_plan_kernel(const int *__restrict__
     }
 }
 
+// -------------------------------------------------------------------------------- plan and block works from the index
+// On the fp32 inference sweep the dense [27][N] tables of levels 1-3 only carried data from rulebook_kernel to the kernels above
+// (and, strided, to a convolution workgroup that compacted its slice while it held a compute unit's matrix pipe): 27 x 4 bytes per
+// row written, read back once or twice.  The entries depend on nothing but the index (bit words + prefix), the output rows'
+// coordinates and the row split, so these kernels make plan and works from those: rulebook_kernel's bit tests feed
+// chunk_plan_kernel's ballots directly.  The same entries in the same order, so the convolutions' sums keep their order.
+struct PlanSource {
+    const unsigned long long *words;  // the INPUT level's index
+    const int *prefix;
+    const int *out_coords;            // [n_out][4] (b, z, y, x): the output level's rows
+    const int *n_out_dev;
+    const int *ranges;                // the convolution launch's row split (resolve_range)
+    int *plan;
+    int64_t plan_stride;
+    fd::IndexGeom gi;
+    int n_out, n_ranges, rows_per_range;
+    int s[3], p[3];                   // stride and padding of the 3 x 3 x 3 window (z, y, x)
+};
+constexpr int kMaxPlanSources = 8;
+struct PlanSources {
+    PlanSource t[kMaxPlanSources];
+};
+
+// rulebook_kernel's test of one tap: the input row at height iz of a column (bit word w, first row `base`), -1 when there is none
+__device__ __forceinline__ int tap_row(unsigned long long w, int base, int iz, int D) {
+    return (iz >= 0 && iz < D && ((w >> iz) & 1ull)) ? base + __popcll(w & ((1ull << iz) - 1ull)) : -1;
+}
+
+// chunk_plan_kernel with the table read replaced by the index lookup.  grid = (widest table's ranges, kPlanSplit, tables): one
+// launch serves several tables, so that their dependent load chains (coordinates -> words / prefixes) overlap instead of running one
+// launch behind the other.  A wave takes the (ky, kx) columns w, w + 4, w + 8 of the window and their three kz taps: a column's word
+// and prefix are loaded once for its taps, all of a chunk's loads are requested before any is used.  No LDS, nothing shared
+// between workgroups.
+__global__ void __launch_bounds__(256) index_plan_kernel(const PlanSources S) {
+    constexpr int TM = sk::kPlanTM, K = sk::kMaxTaps, NH = TM / 64, NCOL = 3;
+    constexpr int kPad = sk::pad_entry(TM);
+    const PlanSource &t = S.t[blockIdx.z];
+    if ((int)blockIdx.x >= t.n_ranges) return;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int r_begin, r_end, n_chunks, chunk_rows;
+    sk::resolve_range_of((int)blockIdx.x, t.n_ranges, t.n_out, t.n_out_dev, t.ranges, t.rows_per_range, r_begin, r_end);
+    if (r_begin < 0 || r_begin >= r_end) return;
+    sk::cut_chunks<TM>(r_begin, r_end, n_chunks, chunk_rows);
+    const fd::IndexGeom gi = t.gi;
+    for (int chunk = blockIdx.y; chunk < n_chunks; chunk += kPlanSplit) {
+        int row0, n_rows;
+        if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
+        int4 c[NH];  // (b, z, y, x)
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const int r = h * 64 + lane;
+            c[h] = reinterpret_cast<const int4 *>(t.out_coords)[row0 + (r < n_rows ? r : n_rows - 1)];  // (clamped address, selected on use)
+        }
+        unsigned long long w[NCOL][NH];
+        int base[NCOL][NH];
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) {
+            const int c9 = wave + 4 * j, ky = c9 / 3, kx = c9 - 3 * ky;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                const int iy = c[h].z * t.s[1] - t.p[1] + ky;
+                const int ix = c[h].w * t.s[2] - t.p[2] + kx;
+                const bool ok = c9 < 9 && h * 64 + lane < n_rows && iy >= 0 && iy < gi.H && ix >= 0 && ix < gi.W;
+                const int64_t col = ok ? fd::col_of(gi, c[h].x, iy, ix) : 0;  // (unconditional loads at a clamped address)
+                const unsigned long long wv = t.words[col];
+                base[j][h] = t.prefix[col];
+                w[j][h] = ok ? wv : 0ull;  // rows past the chunk's end as "no pair"
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NCOL; ++j) {
+            const int c9 = wave + 4 * j;
+            if (c9 >= 9) break;
+            for (int kz = 0; kz < 3; ++kz) {
+                const int k = kz * 9 + c9;
+                int *list = t.plan + (int64_t)k * t.plan_stride + row0;  // [n_rows]
+                int v[NH];
+#pragma unroll
+                for (int h = 0; h < NH; ++h) v[h] = tap_row(w[j][h], base[j][h], c[h].y * t.s[0] - t.p[0] + kz, gi.D);
+                int count = 0;
+#pragma unroll
+                for (int h = 0; h < NH; ++h) {
+                    const unsigned long long m = __ballot(v[h] >= 0);
+                    const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
+                    if (v[h] >= 0) list[pos] = sk::pack_entry(v[h], h * 64 + lane);
+                    count += __popcll(m);
+                }
+#pragma unroll
+                for (int h = 0; h < NH; ++h) {
+                    const int p = h * 64 + lane;
+                    if (p >= count && p < n_rows) list[p] = kPad;
+                }
+                if (lane == 0) reinterpret_cast<unsigned char *>(t.plan + (int64_t)K * t.plan_stride + row0)[k] = (unsigned char)count;
+            }
+        }
+    }
+}
+
+// block_work_kernel for a SubM level (stride 1, padding 1), the table's "entry >= 0" replaced by the bit test: the same work array.
+__global__ void __launch_bounds__(256) index_work_kernel(const unsigned long long *__restrict__ words, fd::IndexGeom g, const int *__restrict__ coords,
+                                                         int n_out, const int *__restrict__ n_out_dev, unsigned row_cost, unsigned *__restrict__ work) {
+    n_out = fd::device_count(n_out, n_out_dev);
+    const int n_blocks = (n_out + kWorkRows - 1) / kWorkRows;
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t o = wave * 64 + lane;
+    if (wave * 8 >= n_blocks) return;
+    const bool in = o < n_out;
+    const int4 c = reinterpret_cast<const int4 *>(coords)[in ? o : n_out - 1];  // (b, z, y, x); clamped address
+    unsigned long long wv[9];
+#pragma unroll
+    for (int c9 = 0; c9 < 9; ++c9) {
+        const int iy = c.z - 1 + c9 / 3, ix = c.w - 1 + c9 % 3;
+        const bool ok = in && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
+        const unsigned long long x = words[ok ? fd::col_of(g, c.x, iy, ix) : 0];
+        wv[c9] = ok ? x : 0ull;
+    }
+    unsigned w = row_cost;
+#pragma unroll
+    for (int c9 = 0; c9 < 9; ++c9) {
+        for (int kz = 0; kz < 3; ++kz) {
+            const int iz = c.y - 1 + kz;
+            const bool v = iz >= 0 && iz < g.D && ((wv[c9] >> iz) & 1ull);
+            const unsigned long long m = __ballot(v);
+            const unsigned byte = (unsigned)(m >> (8 * (lane & 7))) & 0xffu;
+            w += (unsigned)__popc(byte) * 2u + (byte ? 1u : 0u);
+        }
+    }
+    if (lane < 8 && wave * 8 + lane < n_blocks) work[wave * 8 + lane] = w;
+}
+
 }  // namespace
 
 // ---- the chunk plan of a shared rulebook (see fd_spconv_chunk.h and chunk_plan_kernel)
@@ -535,6 +668,71 @@ extern "C" int fd_spconv_plan_build(const int32_t *nbr, int64_t nbr_stride, int 
     hipLaunchKernelGGL(chunk_plan_kernel, dim3((unsigned)n_ranges, kPlanSplit), dim3(256), 0, fd::as_stream(stream_), nbr, nbr_stride, (int)n_out,
                        n_out_dev, ranges, rows_per, plan, plan_stride);
     return fd::check_launch("fd_spconv_plan_build");
+}
+
+// 1 when the layer shape takes its chunk plan straight from the index (fd_spconv_plan_from_index) and runs without a rulebook table:
+// the SubM shapes of fd_spconv_plan_wanted plus the strided 16 -> 32, 32 -> 64 and 64 -> 128 (K = 27, one row set per 128-row chunk).
+// "spconv_plan" = 1 keeps the table route (fd_rulebook + fd_spconv_plan_build) for A/B runs, 2 keeps it for the strided layers only.
+extern "C" int fd_spconv_index_plan_wanted(int cin, int cout, int dtype) {
+    const int knob = fd::tuning(fd::kTuneSpconvPlan);
+    if (knob == 1) return 0;
+    if (cin == cout) return fd_spconv_plan_wanted(cin, cout, dtype);
+    if (dtype != 0 || knob < 0 || knob == 2 || fd::tuning(fd::kTuneSpconvV1)) return 0;
+    if (cin == 16 && fd::tuning(fd::kTuneF32ResRG) >= 32) return 0;  // (16 -> 32 forced onto the resident kernel, which reads the table)
+    return (cin == 16 && cout == 32) || (cin == 32 && cout == 64) || (cin == 64 && cout == 128);
+}
+
+extern "C" int fd_spconv_plan_from_index(int B, int n_sources, const fd_plan_source *sources, fd_stream_t stream_) {
+    FD_REQUIRE(sources && n_sources >= 1 && n_sources <= kMaxPlanSources && B >= 1, "fd_spconv_plan_from_index: need 1 <= n_sources <= 8 and B >= 1");
+    PlanSources S{};
+    int n = 0, width = 0;
+    for (int i = 0; i < n_sources; ++i) {
+        const fd_plan_source &s = sources[i];
+        FD_REQUIRE(s.n_out >= 0 && s.n_out < (1ll << 31), "fd_spconv_plan_from_index: n_out out of range");
+        FD_REQUIRE(s.n_ranges >= 0 && (s.ranges == nullptr || s.n_ranges >= 1), "fd_spconv_plan_from_index: ranges needs n_ranges >= 1");
+        for (int a = 0; a < 3; ++a)
+            FD_REQUIRE(s.stride[a] >= 1 && s.stride[a] <= 4 && s.pad[a] >= 0 && s.pad[a] <= 2, "fd_spconv_plan_from_index: unsupported stride/pad");
+        if (s.n_out == 0) continue;  // an empty level: nothing to write
+        FD_REQUIRE(s.in_words && s.in_prefix && s.out_coords && s.plan, "fd_spconv_plan_from_index: null argument");
+        FD_REQUIRE(s.Din > 0 && s.Din <= 64 && s.Hin > 0 && s.Win > 0, "fd_spconv_plan_from_index: bad grid (D must be <= 64)");
+        FD_REQUIRE(s.plan_stride >= sk::plan_stride_for(s.n_out), "fd_spconv_plan_from_index: plan_stride below fd_spconv_plan_stride(n_out)");
+        PlanSource &t = S.t[n++];
+        t.words = (const unsigned long long *)s.in_words;
+        t.prefix = s.in_prefix;
+        t.out_coords = s.out_coords;
+        t.n_out_dev = s.n_out_dev;
+        t.ranges = s.ranges;
+        t.plan = s.plan;
+        t.plan_stride = s.plan_stride;
+        t.gi = fd::make_geom(B, s.Din, s.Hin, s.Win);
+        t.n_out = (int)s.n_out;
+        t.n_ranges = s.n_ranges;
+        t.rows_per_range = 0;  // the split of the convolution launches (launch_compact / launch_c32)
+        if (!s.ranges) sk::equal_rows_split(t.n_out, sk::kPlanTM, s.n_out_dev != nullptr, t.n_ranges, t.rows_per_range);
+        for (int a = 0; a < 3; ++a) { t.s[a] = s.stride[a]; t.p[a] = s.pad[a]; }
+        width = t.n_ranges > width ? t.n_ranges : width;
+    }
+    if (n == 0) return FD_OK;
+    hipLaunchKernelGGL(index_plan_kernel, dim3((unsigned)width, kPlanSplit, (unsigned)n), dim3(256), 0, fd::as_stream(stream_), S);
+    return fd::check_launch("fd_spconv_plan_from_index");
+}
+
+// fd_spconv_ranges for a SubM level (3 x 3 x 3, stride 1, padding 1) without its table: the block works come from the index
+extern "C" int fd_spconv_ranges_from_index(const uint64_t *words, int B, int D, int H, int W, const int32_t *coords, int64_t n_out,
+                                           const int32_t *n_out_dev, int n_ranges, int32_t *ranges, void *workspace, size_t workspace_bytes,
+                                           fd_stream_t stream_) {
+    FD_REQUIRE(words && coords && ranges && workspace, "fd_spconv_ranges_from_index: null argument");
+    FD_REQUIRE(B >= 1 && D > 0 && D <= 64 && H > 0 && W > 0, "fd_spconv_ranges_from_index: bad grid (D must be <= 64)");
+    FD_REQUIRE(n_ranges >= 1 && n_out >= 0 && n_out < (1ll << 31), "fd_spconv_ranges_from_index: bad sizes");
+    FD_REQUIRE(workspace_bytes >= fd_spconv_ranges_workspace_bytes(n_out), "fd_spconv_ranges_from_index: workspace too small");
+    hipStream_t stream = fd::as_stream(stream_);
+    const int n_blocks = (int)((n_out + kWorkRows - 1) / kWorkRows);
+    unsigned *work = (unsigned *)workspace;
+    if (n_blocks > 0)
+        hipLaunchKernelGGL(index_work_kernel, dim3((unsigned)((n_blocks + 31) / 32)), dim3(256), 0, stream, (const unsigned long long *)words,
+                           fd::make_geom(B, D, H, W), coords, (int)n_out, n_out_dev, (unsigned)kRowCost, work);
+    hipLaunchKernelGGL(range_split_kernel, dim3(1), dim3(1024), 0, stream, work, (int)n_out, n_out_dev, n_ranges, ranges);
+    return fd::check_launch("fd_spconv_ranges_from_index");
 }
 
 #ifdef FD_V2_TRACE

@@ -178,10 +178,14 @@ class SparseIndex(object):
                                 coords.shape[0], _p(row_of), _stream()), "fd_index_lookup")
         return row_of
 
-    def rulebook(self, out_index, ksize, stride, pad):
-        """nbr [K, stride64] int32: input row (in self) feeding each output row of ``out_index`` per tap."""
+    def rulebook(self, out_index, ksize, stride, pad, fp32_layer=None):
+        """nbr [K, stride64] int32: input row (in self) feeding each output row of ``out_index`` per tap.
+        ``fp32_layer = (cin, cout)``: the table is for fp32 inference launches of that (padded) shape only; where their kernels read
+        nothing but a chunk plan (index_plan_wanted) an IndexRulebook comes back instead and no table is built."""
         L = _lib.load()
         assert out_index.n is not None
+        if fp32_layer is not None and index_plan_wanted(self, out_index, ksize, *fp32_layer):
+            return IndexRulebook(self, out_index, stride, pad)
         K = int(ksize[0] * ksize[1] * ksize[2])
         nstride = max(64, (out_index.n + 63) // 64 * 64)
         nbr = torch.empty((K, nstride), dtype=torch.int32, device=self.device)
@@ -201,6 +205,60 @@ class SparseIndex(object):
         nbr.n_in_dev = self.n_dev if src_static else None
         nbr.n_in_expected = self.n_expected if src_static else 0
         return nbr
+
+
+def index_plan_wanted(src, dst, ksize, cin, cout):
+    """True when fp32 launches of a cin -> cout layer from index ``src`` to ``dst`` run on a chunk plan made straight from the index
+    (fd_spconv_index_plan_wanted; 3 x 3 x 3 windows; input rows within the 32-bit gather offsets of the kernels that read a plan)."""
+    return (tuple(int(k) for k in ksize) == (3, 3, 3) and bool(dst.n) and bool(src.n) and src.n < (1 << 23) and src.n * cin * 4 < (1 << 31)
+            and bool(_lib.load().fd_spconv_index_plan_wanted(int(cin), int(cout), 0)))
+
+
+class IndexRulebook(object):
+    """Stands where the K = 27 table of SparseIndex.rulebook would on the fp32 inference sweep: the two indexes and the window, from
+    which plans_from_index / ranges_for write the chunk plans and the equal-work ranges that the kernels read.  Carries the table's
+    attributes (shape, n_out, n_dev, n_expected, ranges, plans), so row_split / plan_for / spconv_apply take it as they take a table;
+    ``table()`` builds the dense table after all, for a caller that needs one (a launch no plan-reading kernel takes)."""
+
+    def __init__(self, src, dst, stride, pad):
+        static = getattr(dst, "static", False)
+        self.src, self.dst, self.stride, self.pad = src, dst, tuple(int(v) for v in stride), tuple(int(v) for v in pad)
+        self.shape = (27, max(64, (dst.n + 63) // 64 * 64))
+        self.device = src.device
+        self.n_out = dst.n
+        self.n_dev = dst.n_dev if static else None
+        self.n_expected = dst.n_expected if static else 0
+        self.ranges, self.plans, self._table = None, {}, None
+
+    def table(self):
+        if self._table is None:
+            self._table = self.src.rulebook(self.dst, (3, 3, 3), self.stride, self.pad)
+        return self._table
+
+
+def plans_from_index(requests):
+    """One fd_spconv_plan_from_index launch for ``requests`` = [(IndexRulebook, ranges, n_ranges)] (the row splits of the launches that
+    will read the plans, see row_split); the plans are cached on the rulebooks as plan_for caches them.  Returns the plan tensors."""
+    L = _lib.load()
+    todo = [(rb, r, int(n), (r.data_ptr() if r is not None else 0, int(n), int(rb.n_out))) for rb, r, n in requests]
+    todo = [t for t in todo if t[3] not in t[0].plans]
+    out = []
+    for at in range(0, len(todo), 8):
+        part = todo[at:at + 8]
+        srcs = (_lib.PlanSource * len(part))()
+        for s, (rb, ranges, n_ranges, key) in zip(srcs, part):
+            pstride = int(L.fd_spconv_plan_stride(rb.n_out))
+            plan = torch.empty((28, pstride), dtype=torch.int32, device=rb.device)
+            s.in_words, s.in_prefix, s.out_coords = rb.src.words.data_ptr(), rb.src.prefix.data_ptr(), rb.dst.coords.data_ptr()
+            s.n_out_dev = rb.n_dev.data_ptr() if rb.n_dev is not None else None
+            s.ranges = ranges.data_ptr() if ranges is not None else None
+            s.plan, s.n_out, s.plan_stride = plan.data_ptr(), rb.n_out, pstride
+            s.Din, s.Hin, s.Win, s.n_ranges = rb.src.D, rb.src.H, rb.src.W, n_ranges
+            s.stride[:], s.pad[:] = list(rb.stride), list(rb.pad)
+            rb.plans[key] = (plan, pstride, ranges)  # (the range table stays alive with the plan cut for it)
+            out.append(plan)
+        check(L.fd_spconv_plan_from_index(part[0][0].src.B, len(part), srcs, _stream()), "fd_spconv_plan_from_index")
+    return out
 
 
 class _PyramidPlan(object):
@@ -319,8 +377,13 @@ def ranges_for(nbr, cin, cout):
         return None, 0
     ranges = torch.empty((n + 1,), dtype=torch.int32, device=nbr.device)
     ws = workspace.get("spconv_ranges", L.fd_spconv_ranges_workspace_bytes(n_out), nbr.device)
-    check(L.fd_spconv_ranges(_p(nbr), nstride, K, n_out, _p(getattr(nbr, "n_dev", None)), n, _p(ranges), _p(ws), ws.numel(), _stream()),
-          "fd_spconv_ranges")
+    if isinstance(nbr, IndexRulebook):  # (a SubM level's: src is dst)
+        ix = nbr.dst
+        check(L.fd_spconv_ranges_from_index(_p(ix.words), ix.B, ix.D, ix.H, ix.W, _p(ix.coords), n_out, _p(nbr.n_dev), n, _p(ranges), _p(ws),
+                                            ws.numel(), _stream()), "fd_spconv_ranges_from_index")
+    else:
+        check(L.fd_spconv_ranges(_p(nbr), nstride, K, n_out, _p(getattr(nbr, "n_dev", None)), n, _p(ranges), _p(ws), ws.numel(), _stream()),
+              "fd_spconv_ranges")
     nbr.ranges = (ranges, n)
     return nbr.ranges
 
@@ -344,6 +407,10 @@ def plan_for(nbr, n_out, ranges, n_ranges):
     rulebook and row split and shared by the convolutions that reuse the rulebook.  Sized by the rulebook's row capacity, no host
     read.  Returns (plan int32[28, stride], stride)."""
     key = (ranges.data_ptr() if ranges is not None else 0, int(n_ranges), int(n_out))
+    if isinstance(nbr, IndexRulebook):
+        assert int(n_out) == nbr.n_out
+        plans_from_index([(nbr, ranges, n_ranges)])
+        return nbr.plans[key][:2]
     plans = getattr(nbr, "plans", None)
     if plans is None:
         plans = nbr.plans = {}
@@ -499,6 +566,9 @@ def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=Fal
     dt = _DT[feats.dtype]
     cin = feats.shape[1]
     out_dtype, out_cols = feats.dtype, cout
+    from_index = isinstance(nbr, IndexRulebook)
+    if from_index and (plan is False or dt != 0 or n_out != nbr.n_out or not index_plan_wanted(nbr.src, nbr.dst, (3, 3, 3), cin, cout)):
+        nbr, from_index = nbr.table(), False  # not a launch that runs on a plan alone: the dense table after all
     K, nstride = nbr.shape
     if out is None:
         out = torch.empty((max(n_out, 1), out_cols), dtype=out_dtype, device=feats.device)[:n_out]
@@ -508,12 +578,13 @@ def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=Fal
     ranges, n_ranges = row_split(nbr, n_out, cin, cout, balanced) if dt == 0 and n_out > 0 else (None, 0)
     # fp32 SubM layers from 32 channels up: the rulebook's chunk plan (plan_for), cut for this launch's row split and shared by the
     # convolutions of the level.  ``plan=False`` (the training path) keeps the in-kernel compaction; the results are the same bits.
+    # An IndexRulebook has no table at all: its plan comes straight from the index, for the strided 16 -> 32 ... 64 -> 128 layers too.
     if plan is None:
-        plan = dt == 0 and n_out > 0 and K == 27 and cin == cout and bool(L.fd_spconv_plan_wanted(cin, cout, 0))
+        plan = from_index or (dt == 0 and n_out > 0 and K == 27 and cin == cout and bool(L.fd_spconv_plan_wanted(cin, cout, 0)))
     if plan:
-        plan_t, pstride = plan_for(_dev(nbr, "nbr", torch.int32), n_out, ranges, n_ranges)
+        plan_t, pstride = plan_for(nbr if from_index else _dev(nbr, "nbr", torch.int32), n_out, ranges, n_ranges)
         check(L.fd_spconv_apply_plan(_p(feats), feats.shape[0], _p(_dev(wpacked, "wpacked")), _p(bias), _p(residual), int(bool(relu)),
-                                     _p(nbr), nstride, _p(ranges), n_ranges, K, n_out, _p(n_dev), int(n_expected or 0),
+                                     None if from_index else _p(nbr), nstride, _p(ranges), n_ranges, K, n_out, _p(n_dev), int(n_expected or 0),
                                      cin, cout, dt, _p(out), _p(plan_t), pstride, _stream()),
               "fd_spconv_apply_plan")
         return out

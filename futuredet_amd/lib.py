@@ -39,6 +39,12 @@ class IndexLevel(ctypes.Structure):  # struct fd_index_level
                 ("coords", c_void_p), ("coords_rows", ctypes.c_int64)]
 
 
+class PlanSource(ctypes.Structure):  # struct fd_plan_source
+    _fields_ = [("in_words", c_void_p), ("in_prefix", c_void_p), ("out_coords", c_void_p), ("n_out_dev", c_void_p), ("ranges", c_void_p),
+                ("plan", c_void_p), ("n_out", ctypes.c_int64), ("plan_stride", ctypes.c_int64), ("Din", ctypes.c_int32), ("Hin", ctypes.c_int32),
+                ("Win", ctypes.c_int32), ("n_ranges", ctypes.c_int32), ("stride", ctypes.c_int32 * 3), ("pad", ctypes.c_int32 * 3)]
+
+
 class ForecastBuffers(ctypes.Structure):  # struct fd_forecast_buffers
     _fields_ = [(n, c_void_p) for n in ("center", "quat", "velocity", "size", "fwd_idx", "fwd_ok", "bwd_idx", "bwd_ok", "match_idx", "cv_centers",
                                         "status", "traj_kind", "traj_src", "traj_first", "traj_group", "n_traj")]
@@ -113,6 +119,10 @@ SIGNATURES = {
     "fd_spconv_plan_build": (c_int, [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     "fd_spconv_apply_plan": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_i64,
                                      c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
+    "fd_spconv_index_plan_wanted": (c_int, [c_int, c_int, c_int]),
+    "fd_spconv_plan_from_index": (c_int, [c_int, c_int, ctypes.POINTER(PlanSource), c_void_p]),
+    "fd_spconv_ranges_from_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
     "fd_densify": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_i64,
                            c_i64, c_i64, c_i64, c_i64, c_void_p]),
     "fd_conv2d_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

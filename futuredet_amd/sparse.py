@@ -299,7 +299,8 @@ class SparseConvolution(SparseModule):
         self._packed[key] = (ver, packed)
         return packed
 
-    def rulebook_for(self, x):
+    def rulebook_for(self, x, fp32_layer=None):
+        """(output index, rulebook) of this convolution on ``x``, shared under the indice_key.  ``fp32_layer``: see SparseIndex.rulebook."""
         data = x.find_indice_pair(self.indice_key)
         if data is not None:
             return data
@@ -311,7 +312,7 @@ class SparseConvolution(SparseModule):
             n_dev = torch.zeros((1,), dtype=torch.int32, device=x.features.device)
             out_index.scan(n_dev)
             out_index.finalize(int(n_dev.cpu()[0]))
-        nbr = x.index.rulebook(out_index, ks, st, pd)
+        nbr = x.index.rulebook(out_index, ks, st, pd, fp32_layer=fp32_layer)
         data = (out_index, nbr)
         if self.indice_key is not None:
             x.indice_dict[self.indice_key] = data
@@ -319,10 +320,12 @@ class SparseConvolution(SparseModule):
 
     def forward(self, x):
         assert isinstance(x, SparseConvTensor)
-        out_index, nbr = self.rulebook_for(x)
         params = [self.weight] + ([self.bias] if self.bias is not None else [])
         if torch.is_grad_enabled() and (x.features.requires_grad or (self.training and any(p.requires_grad for p in params))):
-            return self._forward_autograd(x, out_index, nbr)
+            return self._forward_autograd(x, *self.rulebook_for(x))
+        # an fp32 eval-mode launch: where its kernel reads a chunk plan the plan comes straight from the index, no table is built
+        layer = (pad_channels(self.in_channels), pad_channels(self.out_channels)) if x.features.dtype == torch.float32 and not self.training else None
+        out_index, nbr = self.rulebook_for(x, fp32_layer=layer)
         feats = x.features
         if feats.dtype not in (torch.float32, torch.bfloat16):
             raise NotImplementedError("sparse convolution takes fp32 or bf16 features (features are %s)" % feats.dtype)
@@ -342,6 +345,8 @@ class SparseConvolution(SparseModule):
         _SparseConvFunction."""
         if x.features.dtype not in (torch.float32, torch.bfloat16):
             raise NotImplementedError("sparse convolution training takes fp32 or bf16 features (features are %s)" % x.features.dtype)
+        if isinstance(nbr, hip_ops.IndexRulebook):  # (shared under the indice_key by an eval-mode launch: the gradients read the table)
+            nbr = nbr.table()
         K = int(np.prod(self.kernel_size))
         cin_p, cout_p = pad_channels(self.in_channels), pad_channels(self.out_channels)
         F = torch.nn.functional

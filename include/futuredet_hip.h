@@ -171,6 +171,30 @@ int fd_spconv_apply_plan(const void *in_feats, int64_t n_in, const void *wpacked
                          const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
                          const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats, const int32_t *plan,
                          int64_t plan_stride, fd_stream_t stream);
+/* The chunk plan straight from the sparse index, without the rulebook table in between (fp32; 3 x 3 x 3 windows only: SubM, and
+ * the strided convolutions into the next level).  fd_spconv_plan_from_index writes, in ONE launch, the plans of up to 8 sources:
+ * source i is the table fd_rulebook would make from (in_words, in_prefix, Din/Hin/Win, out_coords, n_out_dev, {3,3,3}, stride, pad),
+ * cut for the row split (ranges, n_ranges) as fd_spconv_plan_build cuts it -- the same int32 [28, plan_stride] words for every
+ * column below the row count.  out_coords holds n_out rows.  fd_spconv_ranges_from_index is fd_spconv_ranges for a SubM level
+ * (stride 1, pad 1; words / coords of the level itself): the same table bit for bit, same workspace size.
+ * fd_spconv_index_plan_wanted: 1 for the layer shapes whose kernels read nothing but such a plan -- fd_spconv_apply_plan then takes
+ * nbr == NULL (nbr_stride is ignored).  For every other shape, or without a plan, nbr == NULL is FD_EINVAL. */
+typedef struct fd_plan_source {
+    const uint64_t *in_words; /* index of the INPUT level */
+    const int32_t *in_prefix;
+    const int32_t *out_coords; /* [n_out, 4] (b, z, y, x): rows of the output level */
+    const int32_t *n_out_dev;  /* NULL, or the device's row count (n_out is then a capacity) */
+    const int32_t *ranges;     /* the row split of the convolution launch, as for fd_spconv_plan_build */
+    int32_t *plan;             /* [28, plan_stride] */
+    int64_t n_out, plan_stride;
+    int32_t Din, Hin, Win, n_ranges;
+    int32_t stride[3], pad[3];
+} fd_plan_source;
+int fd_spconv_index_plan_wanted(int cin, int cout, int dtype);
+int fd_spconv_plan_from_index(int B, int n_sources, const fd_plan_source *sources_host, fd_stream_t stream);
+int fd_spconv_ranges_from_index(const uint64_t *words, int B, int D, int H, int W, const int32_t *coords, int64_t n_out,
+                                const int32_t *n_out_dev, int n_ranges, int32_t *ranges /*[n_ranges+1]*/, void *workspace,
+                                size_t workspace_bytes, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Densify.  Replaces SparseConvTensor.dense() + view (scn.py:165-168): out[b, c*D + d, y, x] = feats[row, c].
