@@ -1799,6 +1799,89 @@ def augment_boxes(boxes, counts, recs, out=None):
     return out
 
 
+# ---- training: the GT range filter and the bev-mask warp (fd_augment_map.hip) -----------------------------------------------------
+AUGMENT_MASK_RECORD_DOUBLES = ctypes.sizeof(_lib.AugmentMaskRecord) // 8  # a mask record travels as 13 float64 words (104 bytes)
+
+
+def gt_range_filter(boxes, counts, classes, pc_range, trajectory=None, out=None, status=None):
+    """fd_gt_range_filter: drops, at every timestep, the objects whose timestep-0 box has no BEV corner strictly inside ``pc_range``
+    (xmin, ymin, xmax, ymax) and moves the kept rows to the front.  boxes [B, T, n_max, 12] fp32, counts [B, T] int32, classes and
+    ``trajectory`` (or None) [B, T, n_max] int32, all on the device.  ``out``: None = new tensors, "inplace" = the inputs themselves, or
+    a tuple (boxes, counts, classes, trajectory | None) of tensors shaped like the inputs (each may be its input).  Rows at or past the
+    new counts are zeros.  ``status`` int32 [B] (None: new) receives the number of timesteps whose count differs from timestep 0's.
+    Returns (boxes, counts, classes, trajectory | None, status).  One launch, no synchronisation."""
+    boxes = _dev(boxes, "boxes", torch.float32)
+    if boxes.dim() != 4 or boxes.shape[3] != 12 or min(boxes.shape[:3]) < 1:
+        raise FutureDetHipError("gt_range_filter: boxes must be [B, T, n_max, 12] with B, T, n_max >= 1 (got %s)" % (tuple(boxes.shape),))
+    B, T, n_max = (int(v) for v in boxes.shape[:3])
+    ins = [boxes, _dev(counts, "counts", torch.int32), _dev(classes, "classes", torch.int32),
+           _dev(trajectory, "trajectory", torch.int32) if trajectory is not None else None]
+    shapes = [tuple(boxes.shape), (B, T), (B, T, n_max), (B, T, n_max)]
+    names = ["boxes", "counts", "classes", "trajectory"]
+    for t, shape, name in zip(ins, shapes, names):
+        if t is not None and (tuple(t.shape) != shape or t.device != boxes.device):
+            raise FutureDetHipError("gt_range_filter: %s must be %s on %s (got %s on %s)" % (name, list(shape), boxes.device, tuple(t.shape), t.device))
+    rng = [float(v) for v in pc_range]
+    if len(rng) != 4:
+        raise FutureDetHipError("gt_range_filter: pc_range takes (xmin, ymin, xmax, ymax), got %d values" % len(rng))
+    if isinstance(out, str):
+        if out != "inplace":
+            raise FutureDetHipError("gt_range_filter: out must be None, \"inplace\" or a tuple of four tensors")
+        outs = list(ins)
+    elif out is None:
+        outs = [torch.empty_like(t) if t is not None else None for t in ins]
+    else:
+        outs = list(out)
+        if len(outs) != 4:
+            raise FutureDetHipError("gt_range_filter: out takes (boxes, counts, classes, trajectory | None)")
+        for i, (t, src, name) in enumerate(zip(outs, ins, names)):
+            if src is None:
+                outs[i] = None
+                continue
+            t = _dev(t, name + "_out", src.dtype)
+            if tuple(t.shape) != tuple(src.shape) or t.device != src.device:
+                raise FutureDetHipError("gt_range_filter: %s_out %s does not match %s %s" % (name, tuple(t.shape), name, tuple(src.shape)))
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=boxes.device)
+    status = _dev(status, "status", torch.int32)
+    if status.numel() != B or status.device != boxes.device:
+        raise FutureDetHipError("gt_range_filter: status must be int32 [%d] on %s (got %s)" % (B, boxes.device, tuple(status.shape)))
+    check(_lib.load().fd_gt_range_filter(_p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), rng[0], rng[1], rng[2], rng[3], _p(outs[0]), _p(outs[1]),
+                                         _p(outs[2]), _p(outs[3]), _p(status), B, T, n_max, _stream()), "fd_gt_range_filter")
+    return outs[0], outs[1], outs[2], outs[3], status
+
+
+def augment_mask_check(recs, H, W):
+    """fd_augment_mask_check on host records (a numpy array [B] of augment.MASK_RECORD_DTYPE): raises when a matrix would map a pixel of
+    an H x W plane out of the fixed-point range.  No device work."""
+    import numpy as np
+
+    recs = np.ascontiguousarray(recs)
+    if recs.dtype.itemsize != 8 * AUGMENT_MASK_RECORD_DOUBLES or recs.ndim != 1 or recs.shape[0] < 1:
+        raise FutureDetHipError("augment_mask_check: recs must be a vector of %d-byte mask records" % (8 * AUGMENT_MASK_RECORD_DOUBLES))
+    check(_lib.load().fd_augment_mask_check(ctypes.c_void_p(recs.ctypes.data), int(recs.shape[0]), int(H), int(W)), "fd_augment_mask_check")
+
+
+def augment_mask(src, recs, out=None):
+    """fd_augment_mask: out [B, C, H, W] fp32 = warp(warp(flip(src), m1), m2) per plane with recs [B] (float64 [B, 13] on the device,
+    GlobalAugment.mask_record's upload).  ``out`` None: a new tensor; it must not be src.  One launch, no synchronisation."""
+    src = _dev(src, "src", torch.float32)
+    if src.dim() != 4 or min(src.shape) < 1:
+        raise FutureDetHipError("augment_mask: src must be [B, C, H, W] with no empty axis (got %s)" % (tuple(src.shape),))
+    B, C, H, W = (int(v) for v in src.shape)
+    recs = _dev(recs, "recs", torch.float64)
+    if recs.numel() != B * AUGMENT_MASK_RECORD_DOUBLES or recs.device != src.device:
+        raise FutureDetHipError("augment_mask: recs must hold %d record(s) of %d float64 words on %s (augment.GlobalAugment.mask_record), got %s"
+                                % (B, AUGMENT_MASK_RECORD_DOUBLES, src.device, tuple(recs.shape)))
+    if out is None:
+        out = torch.empty_like(src)
+    out = _dev(out, "out", torch.float32)
+    if tuple(out.shape) != tuple(src.shape) or out.device != src.device:
+        raise FutureDetHipError("augment_mask: out %s does not match src %s" % (tuple(out.shape), tuple(src.shape)))
+    check(_lib.load().fd_augment_mask(_p(src), _p(recs), _p(out), B, C, H, W, _stream()), "fd_augment_mask")
+    return out
+
+
 # ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------
 LOSS_MAPS = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")  # fd_loss_task.maps / d_maps, in this order
 

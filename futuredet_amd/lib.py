@@ -87,6 +87,10 @@ class AugmentRecord(ctypes.Structure):  # struct fd_augment_record
                 ("tx", ctypes.c_double), ("ty", ctypes.c_double), ("tz", ctypes.c_double)]
 
 
+class AugmentMaskRecord(ctypes.Structure):  # struct fd_augment_mask_record
+    _fields_ = [("flip_a", ctypes.c_int32), ("flip_b", ctypes.c_int32), ("m1", ctypes.c_double * 6), ("m2", ctypes.c_double * 6)]
+
+
 # name -> (restype, argtypes); this table is checked against include/futuredet_hip.h by the tests
 SIGNATURES = {
     "fd_abi_version": (c_int, []),
@@ -240,6 +244,10 @@ SIGNATURES = {
     "fd_levels_overflow": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fd_augment_points": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fd_augment_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fd_gt_range_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fd_augment_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fd_augment_mask_check": (c_int, [c_void_p, c_int, c_int, c_int]),
     "fd_loss_chunk": (c_int, []),
     "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),

@@ -352,7 +352,7 @@ class _StaticTrainBase(object):
         return None
 
     def _init_common(self, model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
-                     augment=None):
+                     augment=None, filter_gt=False):
         name = self.name
         self._check_model(model)
         head = model.bbox_head
@@ -384,6 +384,20 @@ class _StaticTrainBase(object):
         # augment (augment.GlobalAugment or None): the records of fd_augment_points / fd_augment_boxes, one per cloud, and the last draw
         self.augment, self.last_aug_params = augment, None
         self.aug_rec = torch.zeros((B, hip_ops.AUGMENT_RECORD_DOUBLES), dtype=torch.float64, device=dev) if augment is not None else None
+        # augment.warp_bev: the step warps the batch's unwarped map into self.bev itself (fd_augment_mask), one record per sample
+        self.mask_rec = None
+        if self.bev is not None and getattr(augment, "warp_bev", False):
+            from .augment import check_bev_size
+
+            check_bev_size(self.bev)
+            self.mask_rec = torch.zeros((B, hip_ops.AUGMENT_MASK_RECORD_DOUBLES), dtype=torch.float64, device=dev)
+        # filter_gt: the reference's train-mode range filter (fd_gt_range_filter) on the static ground truth, over the voxel range
+        self.filter_gt, self.gt_range, self.gt_filter_status = bool(filter_gt), None, None
+        if self.filter_gt:
+            from .augment import bev_range
+
+            self.gt_range = bev_range(voxel_cfg["range"])
+            self.gt_filter_status = torch.zeros((B,), dtype=torch.int32, device=dev)
         self._ring, self._slot = None, 0
         self.iteration = 0
         self.outputs, self.level_counts = None, None
@@ -397,11 +411,13 @@ class _StaticTrainBase(object):
     # -- inputs
     def _pinned(self):
         """a slot of the ring of pinned staging buffers (cloud counts, the six scalars, the event of its last copy, the augmentation
-        records), free again once its last copy has run"""
+        records, the mask records), free again once its last copy has run"""
         if self._ring is None:
             self._ring = [[torch.empty((self.B,), dtype=torch.int32).pin_memory(), torch.empty((6,), dtype=torch.float64).pin_memory(), None,
                            torch.empty((self.B, hip_ops.AUGMENT_RECORD_DOUBLES), dtype=torch.float64).pin_memory()
-                           if self.augment is not None else None]
+                           if self.augment is not None else None,
+                           torch.empty((self.B, hip_ops.AUGMENT_MASK_RECORD_DOUBLES), dtype=torch.float64).pin_memory()
+                           if getattr(self, "mask_rec", None) is not None else None]
                           for _ in range(8)]
         slot = self._ring[self._slot % len(self._ring)]
         self._slot += 1
@@ -410,13 +426,13 @@ class _StaticTrainBase(object):
         return slot
 
     def _aug_params(self, batch):
-        """this batch's augmentation parameters [B, 7]: batch["aug_params"], else a draw (not for a bev_map head, whose map must have
-        been warped with the same parameters by whoever made the batch)"""
+        """this batch's augmentation parameters [B, 7]: batch["aug_params"], else a draw (for a bev_map head only with augment.warp_bev:
+        otherwise its map must have been warped with the same parameters by whoever made the batch)"""
         from .augment import PARAM_FIELDS
 
         params = batch.get("aug_params")
         if params is None:
-            if self.bev is not None:
+            if self.bev is not None and not getattr(self.augment, "warp_bev", False):
                 raise ValueError("%s: augment with a bev_map head needs batch[\"aug_params\"] [%d, %d] and a \"bev_map\" already warped "
                                  "with them (the map warp, get_mask, is not built)" % (self.name, self.B, len(PARAM_FIELDS)))
             params = self.augment.draw(self.B)
@@ -431,6 +447,8 @@ class _StaticTrainBase(object):
             raise ValueError("the step was built for batches of %d clouds, got %d" % (self.B, len(clouds)))
         aug = self.augment
         params = self._aug_params(batch) if aug is not None else None  # (drawn or refused before anything of the step changes)
+        warp = getattr(self, "mask_rec", None) is not None
+        mask_recs = aug.mask_record(params) if warp else None
         if self.bev is not None:
             bev = batch.get("bev_map")
             if bev is None:
@@ -447,6 +465,9 @@ class _StaticTrainBase(object):
             slot[3].numpy()[:] = aug.record(params).view(np.float64).reshape(self.B, -1)
             self.aug_rec.copy_(slot[3], non_blocking=True)
             self.last_aug_params = params
+            if warp:
+                slot[4].numpy()[:] = mask_recs.view(np.float64).reshape(self.B, -1)
+                self.mask_rec.copy_(slot[4], non_blocking=True)
         for b, c in enumerate(clouds):
             n = int(c.shape[0])
             if n > self.capacity or c.shape[1] != self.ndim:
@@ -470,12 +491,20 @@ class _StaticTrainBase(object):
             self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
             if aug is not None:  # narrower than the buffer: in place, the counts never reach past column n
                 hip_ops.augment_boxes(self.gt_boxes, gcounts, self.aug_rec, out=self.gt_boxes)
-        self.gt_counts.copy_(gcounts, non_blocking=True)
+        filter_gt = getattr(self, "filter_gt", False)
+        if not filter_gt:
+            self.gt_counts.copy_(gcounts, non_blocking=True)
         self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
         if self.gt_trajectory is not None:
             self.gt_trajectory[:, :, :n].copy_(batch["gt_trajectory"], non_blocking=True)
+        if filter_gt:  # in place on the static rows; the kernel reads the batch's counts and writes the step's
+            hip_ops.gt_range_filter(self.gt_boxes, gcounts.contiguous(), self.gt_classes, self.gt_range, trajectory=self.gt_trajectory,
+                                    out=(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_trajectory), status=self.gt_filter_status)
         if self.bev is not None:
-            self.bev.copy_(batch["bev_map"], non_blocking=True)
+            if warp:  # the batch's map is the unwarped one
+                hip_ops.augment_mask(batch["bev_map"].contiguous(), self.mask_rec, out=self.bev)
+            else:
+                self.bev.copy_(batch["bev_map"], non_blocking=True)
 
     # -- the step
     def _body(self, static):
@@ -567,8 +596,16 @@ class StaticTrainStep(_StaticTrainBase):
     ``augment`` (an augment.GlobalAugment; None = none, today's launches): the step draws one set of parameters per cloud (or takes
     batch["aug_params"] [B, 7]), keeps them in ``last_aug_params``, uploads their records through the staging ring, and loads the
     batch through fd_augment_points -- one launch per cloud, shuffle and transforms, in place of the copy -- and one fd_augment_boxes.
-    The warm-up and the overflow re-run read the static buffers, so they see the augmented batch once.  With a bev_map head the map
-    warp is not built: the batch must carry ``aug_params`` and a ``bev_map`` already warped with them, else ValueError.
+    The warm-up and the overflow re-run read the static buffers, so they see the augmented batch once.  With a bev_map head and
+    ``GlobalAugment(..., warp_bev=True)`` the batch carries the UNWARPED ``bev_map`` [B, 6, 180, 180]: the step uploads one mask record
+    per sample through the same ring and warps the map into ``self.bev`` with fd_augment_mask (the reference's ``get_mask``) in place
+    of the copy.  With ``warp_bev=False`` the batch must carry ``aug_params`` and a ``bev_map`` already warped with them, else
+    ValueError.
+
+    ``filter_gt`` (False = today's launches): after the boxes are loaded (and augmented), fd_gt_range_filter drops, at every
+    timestep, the objects whose timestep-0 box has no BEV corner inside the x / y bounds of ``voxel_cfg["range"]`` -- the train-mode
+    filter of the reference's Voxelization stage -- in place on the static ground truth; ``gt_counts`` is then written by the kernel
+    and ``gt_filter_status`` [B] counts the timesteps of a sample whose count differed from timestep 0's.  Works with ``augment=None``.
 
     ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
     device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward
@@ -578,9 +615,9 @@ class StaticTrainStep(_StaticTrainBase):
     name = "StaticTrainStep"
 
     def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
-                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False, augment=None):
+                 max_gt=None, timesteps=None, row_caps="auto", headroom=1.5, graph=False, augment=None, filter_gt=False):
         self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
-                          augment)
+                          augment, filter_gt)
         self.row_caps_mode, self.headroom = row_caps, float(headroom)
         self.skip = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self.expected, self.caps, self.caps_dev = None, None, None
@@ -670,14 +707,14 @@ class StaticPillarsTrainStep(_StaticTrainBase):
     There are no row capacities and no overflow guard: the voxeliser caps the pillars of a cloud at max_voxel_num[0] and every buffer
     has that size, so ``overflowed()`` is False and ``check`` reads nothing back.  Needs bbox_head.fused_loss; a bev_map head takes
     batch["bev_map"]; neck / bbox_head train_dtype = torch.bfloat16 and the dense fused_bn switches work as in train_steps.  The
-    reader trains in fp32.  ``augment``: as for StaticTrainStep.  ``graph``: only False, as for StaticTrainStep."""
+    reader trains in fp32.  ``augment``, ``filter_gt``: as for StaticTrainStep.  ``graph``: only False, as for StaticTrainStep."""
 
     name = "StaticPillarsTrainStep"
 
     def __init__(self, model, voxel_cfg, assigner, optimizer, scheduler=None, grad_clip=None, capacity=400000, batch_size=1, ndim=5,
-                 max_gt=None, timesteps=None, graph=False, augment=None):
+                 max_gt=None, timesteps=None, graph=False, augment=None, filter_gt=False):
         self._init_common(model, voxel_cfg, assigner, optimizer, scheduler, grad_clip, capacity, batch_size, ndim, max_gt, timesteps, graph,
-                          augment)
+                          augment, filter_gt)
         if not 1 <= self.B <= 16:
             raise ValueError("StaticPillarsTrainStep: the pillar reader takes 1 to 16 clouds per batch (got %d)" % self.B)
 

@@ -849,6 +849,68 @@ int fd_augment_boxes(const float *boxes, const int32_t *counts, const fd_augment
                      fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Training: what the reference does between the augmentation and AssignLabel (fd_augment_map.hip) -- the ground-truth range filter of
+ * the train-mode Voxelization stage (det3d/datasets/pipelines/preprocess.py:249-255, prep.filter_gt_box_outside_range,
+ * det3d/core/sampler/preprocess.py:113-127) and the warp of a bev_map head's mask (get_mask, preprocess.py:75-90, 212).
+ * Purely additive: fd_abi_version() stays 8.  One launch each, graph-capturable, no atomics, no allocation, no workspace, no
+ * synchronisation.
+ *
+ * fd_gt_range_filter: boxes [B, T, n_max, 12] fp32 (16-byte aligned), counts [B, T] int32, classes [B, T, n_max] int32, trajectory
+ *   [B, T, n_max] int32 or NULL (then trajectory_out is ignored), all in device memory; the range (xmin, ymin, xmax, ymax) by value.
+ *   The mask of sample b comes from the rows of timestep 0: with c0 = clamp(counts[b, 0], 0, n_max), object i < c0 is KEPT iff at
+ *   least one of the four BEV corners of boxes[b, 0, i] lies strictly inside the range rectangle.  Every operation below is one fp32
+ *   IEEE operation rounded on its own unless said otherwise (box_np_ops.center_to_corner_box2d -> corners_nd / rotation_2d):
+ *     w, l = columns 3, 4; angle a = column 11 (the LAST column); s = fl32(sin(double(a))), c = fl32(cos(double(a))) (the reference
+ *       takes NumPy's fp32 sin / cos, which lie within 1.5 ulp of these);
+ *     corner k = 0..3, in the reference's order, has the offsets (ox, oy) = (-w/2, -l/2), (-w/2, +l/2), (+w/2, +l/2), (+w/2, -l/2);
+ *     x_k = (ox c + oy s) + column 0,  y_k = (-(ox s) + oy c) + column 1   (rotation_2d: clockwise for a positive angle);
+ *     the rectangle's vertices, as minmax_to_corner_2d builds them: x0 = xmin, x1 = xmin + (xmax - xmin), y0 = ymin,
+ *       y1 = ymin + (ymax - ymin); P0 = (x0, y0), P1 = (x0, y1), P2 = (x1, y1), P3 = (x1, y0), edge vector V_j = P_j - P_(j-1 mod 4);
+ *     inside (points_in_convex_polygon_jit, geometry.py:280): for every j, double(V_j.y (P_j.x - x_k)) - double(V_j.x (P_j.y - y_k))
+ *       is NOT >= 0.  A corner exactly on a boundary line is therefore outside; a NaN corner counts as inside, as in the reference.
+ *   The same mask is applied to every timestep t: with m = min(clamp(counts[b, t], 0, n_max), c0), the kept rows i < m of boxes,
+ *   classes and trajectory move to the front in their order, counts_out[b, t] = their number, and every row at or past that number is
+ *   PADDING, written as zeros (boxes 0.0f, classes 0, trajectory 0) up to n_max.  status[b] = the number of timesteps t with
+ *   counts[b, t] != counts[b, 0] (the reference fails there: a boolean index of the wrong length); rows i >= c0 of such a step are
+ *   dropped.  Each output may be its input (in place) or must not overlap it; outputs must not overlap one another.
+ *   FD_EINVAL for: B or T < 1, n_max outside [1, FD_RANGE_FILTER_MAX_N], more than FD_AUGMENT_MAX_ROWS rows, a null pointer other
+ *   than trajectory / trajectory_out, a trajectory without trajectory_out, boxes not 16-byte or int arrays not 4-byte aligned, a
+ *   partial overlap of an output with its input, a range that is not finite or has xmax <= xmin or ymax <= ymin.
+ *
+ * fd_augment_mask: src, dst [B, C, H, W] fp32, recs [B] in device memory (8-byte aligned); dst must not overlap src.  Per plane
+ *   dst = warp(warp(flip(src), m1), m2): flip_a reverses the W axis (np.fliplr of the reference's HWC mask), flip_b the H axis, both
+ *   before the warps; m1, m2 are the INVERSE 2x3 matrices of the two warps, row-major.  warp(s, m) is OpenCV's classic warpAffine with
+ *   INTER_LINEAR and a constant border of 0 on fp32; for the destination pixel (x, y):
+ *     X = (rint((m[1] y + m[2]) 1024) + 16 + rint(m[0] x 1024)) >> 5,  Y = (rint((m[4] y + m[5]) 1024) + 16 + rint(m[3] x 1024)) >> 5
+ *       (float64 products and sums rounded one by one, rint = round half to even, int32 with arithmetic shifts);
+ *     sx = X >> 5, sy = Y >> 5, fx = float(X & 31) / 32, fy = float(Y & 31) / 32;
+ *     w00 = (1 - fy)(1 - fx), w01 = (1 - fy) fx, w10 = fy (1 - fx), w11 = fy fx  (fp32);
+ *     out = s[sy][sx] w00 + s[sy][sx + 1] w01 + s[sy + 1][sx] w10 + s[sy + 1][sx + 1] w11  (fp32, left to right, no fused
+ *       multiply-add); every tap outside the plane reads 0.
+ *   The intermediate plane lives in LDS (H W 4 bytes, one workgroup per plane).  The kernel reads nothing out of bounds whatever a
+ *   record holds (a float64 coordinate is clamped to +-2^29 before it becomes an int32, which only moves taps that lie far outside
+ *   the plane anyway), but the definition above holds only for records that fd_augment_mask_check accepts.
+ *   FD_EINVAL for: B, C, H or W < 1, H W > FD_AUGMENT_MASK_MAX_PIXELS, B C H W > FD_AUGMENT_MAX_ROWS, null or misaligned pointers
+ *   (src / dst 4 bytes, recs 8), overlapping src and dst.  FD_ELAUNCH when the runtime refuses the LDS allocation.
+ * fd_augment_mask_check: host-only, recs_host [B] in HOST memory.  FD_EINVAL when a coefficient is not finite or when, for some
+ *   pixel of an H x W plane, a fixed-point coordinate could leave int32 or sx / sy could leave int16 (OpenCV's own map format):
+ *   accepted iff |m[0]| (W - 1) + |m[1]| (H - 1) + |m[2]| < FD_AUGMENT_MASK_MAX_COORD, and likewise for m[3], m[4], m[5], for both
+ *   matrices.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_RANGE_FILTER_MAX_N 4096
+#define FD_AUGMENT_MASK_MAX_PIXELS 40960
+#define FD_AUGMENT_MASK_MAX_COORD 32000.0
+typedef struct fd_augment_mask_record {
+    int32_t flip_a, flip_b;
+    double m1[6], m2[6];
+} fd_augment_mask_record;
+int fd_gt_range_filter(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory, float xmin, float ymin,
+                       float xmax, float ymax, float *boxes_out, int32_t *counts_out, int32_t *classes_out, int32_t *trajectory_out,
+                       int32_t *status, int B, int T, int n_max, fd_stream_t stream);
+int fd_augment_mask(const float *src, const fd_augment_mask_record *recs, float *dst, int B, int C, int H, int W, fd_stream_t stream);
+int fd_augment_mask_check(const fd_augment_mask_record *recs_host, int B, int H, int W);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
  * det3d/models/losses/centernet_loss.py as center_head.py:396-539 combines them, forward terms and the gradient of every head map.
  * Purely additive: fd_abi_version() stays 8.  fp32 maps, contiguous [B, channels, H, W].
