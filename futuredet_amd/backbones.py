@@ -210,11 +210,11 @@ class SpMiddleResNetFHD(nn.Module):
                 rb_cache[key] = src.rulebook(dst, ks, st, pd, fp32_layer=layer)
             return rb_cache[key]
 
-        def run(conv, bn, x, src, dst, relu, residual=None):
+        def run(conv, bn, x, src, dst, relu, residual=None, layout=0):
             wpk, bias, cin_p, cout_p = conv.packed_weight(dt, bn)
             assert x.shape[1] == cin_p, (x.shape, cin_p)
             nbr = rulebook(src, dst, conv)
-            fn = lambda: hip_ops.spconv_apply(x, wpk, bias, nbr, dst.n, cout_p, residual=residual, relu=relu)  # noqa: E731
+            fn = lambda: hip_ops.spconv_apply(x, wpk, bias, nbr, dst.n, cout_p, residual=residual, relu=relu, layout=layout)  # noqa: E731
             if self.profile_hook is not None:
                 s = 4 if dt == torch.float32 else 2
                 K = nbr.shape[0]
@@ -289,10 +289,16 @@ class SpMiddleResNetFHD(nn.Module):
             dst = idx[lvl]
             if lvl == 1 and side is not None:
                 main.wait_stream(side)  # join: the first level's convolutions are issued, the other levels' rulebooks are needed now
-            x = run(conv, bn, x, src, dst, relu=True)
-            for blk in blocks:
-                y = run(blk.conv1, blk.bn1, x, dst, dst, relu=True)
-                x = run(blk.conv2, blk.bn2, y, dst, dst, relu=True, residual=x)
+            # The tensors between the strided convolution into a level and the level's last convolution are read by these launches alone:
+            # on the fp32 plan route they are stored bank-spread (fd_spconv_apply_layout: 1 input, 2 residual, 4 output), so that their
+            # gathers do not queue on one bank.  The level's last output -- levels[lvl], the next strided layer, densify -- stays plain.
+            swz = from_index and lvl >= 1 and len(blocks) > 0 and hip_ops.level_layout(
+                spconv.pad_channels(conv.in_channels), spconv.pad_channels(conv.out_channels), src.n, dst.n)
+            x = run(conv, bn, x, src, dst, relu=True, layout=4 if swz else 0)
+            for i, blk in enumerate(blocks):
+                y = run(blk.conv1, blk.bn1, x, dst, dst, relu=True, layout=5 if swz else 0)
+                last = i + 1 == len(blocks)
+                x = run(blk.conv2, blk.bn2, y, dst, dst, relu=True, residual=x, layout=(3 if last else 7) if swz else 0)
             levels[lvl] = (x, dst)
         bev = hip_ops.densify(x, idx[4], out_dtype=self.dense_dtype or dt, channels_last=self.dense_channels_last, out=dense_out)
         return bev, levels

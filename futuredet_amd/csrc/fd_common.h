@@ -33,6 +33,7 @@ struct SpconvCall {
     hipStream_t stream;
     const int *plan;  // null, or the rulebook's chunk plan (fd_spconv_plan_build for the same n_out / ranges / n_ranges): fd_spconv_chunk.h
     int64_t plan_stride;
+    int layout;  // which tensors are stored bank-spread (fd_spconv_apply_layout; skeleton::kLayoutIn / Residual / Out), 0 = none
 };
 
 constexpr int kSpconvMaxTaps = 27;  // 3 x 3 x 3: the largest kernel of every sparse-convolution entry point
@@ -127,7 +128,7 @@ bool ensure_dynamic_lds(const void *kernel, size_t bytes, std::atomic<uint64_t> 
     X(kTuneSpconvRG, "spconv_rg") X(kTuneSpconvV1, "spconv_v1") X(kTuneConvNT, "conv_nt") X(kTuneV2RangesPerCU, "v2_ranges_per_cu") \
     X(kTuneSpconvC32, "spconv_c32") X(kTuneBf16GP, "bf16_gp") X(kTuneBf16RG, "bf16_rg") X(kTuneBf16Depth, "bf16_depth")        \
     X(kTuneBf16NW, "bf16_nw") X(kTuneBf16Win, "bf16_win") X(kTuneF32ResRG, "f32_res_rg") X(kTuneConvStrip, "conv_strip")       \
-    X(kTuneF32ResNW, "f32_res_nw") X(kTuneSpconvPlan, "spconv_plan")
+    X(kTuneF32ResNW, "f32_res_nw") X(kTuneSpconvPlan, "spconv_plan") X(kTuneSpconvSwz, "spconv_swz")
 #define FD_TUNE_ENUM(key, name) key,
 enum TuneKey { FD_TUNE_KNOBS(FD_TUNE_ENUM) kTuneCount };
 #undef FD_TUNE_ENUM

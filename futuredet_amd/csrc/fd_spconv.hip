@@ -267,7 +267,7 @@ extern "C" int fd_spconv_pack_weight(const float *w, int K, int cin, int cout, i
 namespace {
 int spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu, const int32_t *nbr,
                  int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out, const int32_t *n_out_dev, int64_t n_expected, int cin,
-                 int cout, int dtype, void *out_feats, fd_stream_t stream, const int32_t *plan, int64_t plan_stride) {
+                 int cout, int dtype, void *out_feats, fd_stream_t stream, const int32_t *plan, int64_t plan_stride, int layout = 0) {
     FD_REQUIRE(K >= 1 && K <= fd::kSpconvMaxTaps, "fd_spconv_apply: K must be in [1,27]");
     FD_REQUIRE(dtype == 0 || dtype == 1, "fd_spconv_apply: dtype must be 0 (f32) or 1 (bf16)");
     FD_REQUIRE(n_out >= 0 && n_out <= nbr_stride && n_out < (1ll << 31), "fd_spconv_apply: n_out out of range");
@@ -276,7 +276,21 @@ int spconv_apply(const void *in_feats, int64_t n_in, const void *wpacked, const 
     if (n_out == 0) return FD_OK;  // an empty active set (empty cloud): nothing to compute, buffers may be null
     FD_REQUIRE(in_feats && wpacked && (nbr || plan) && out_feats, "fd_spconv_apply: null argument");
     const fd::SpconvCall c{in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, (int)n_out, n_out_dev, n_expected,
-                           cin, cout, dtype, out_feats, fd::as_stream(stream), plan, plan_stride};
+                           cin, cout, dtype, out_feats, fd::as_stream(stream), plan, plan_stride, layout};
+    if (layout) {
+        // bank-spread tensors (fd_spconv_apply_layout): only the pair-compacting fp32 kernels read or write them, and only in the
+        // instantiations built for it -- every other launch is refused, nothing falls back to a kernel that would read plain rows
+        FD_REQUIRE((layout & ~7) == 0, "fd_spconv_apply_layout: layout has bits 0 (input), 1 (residual), 2 (output)");
+        int launched = 0;
+        if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1)) {
+            if (fd::tuning(fd::kTuneSpconvC32) >= 0) launched = fd::spconv_f32_c32_dispatch(c);
+            if (!launched) launched = fd::spconv_f32_compact_dispatch(c);
+        }
+        if (launched) return fd::check_launch("fd_spconv_apply_layout");
+        fd::set_error("fd_spconv_apply_layout: no kernel runs %d -> %d (dtype %d) with layout %d: bank-spread rows are for the fp32 32 -> 32, 64 -> 64 and "
+                      "128 -> 128 layers (all bits) and the outputs of 16 -> 32, 32 -> 64 and 64 -> 128 (bit 2)", cin, cout, dtype, layout);
+        return FD_EINVAL;
+    }
     if (dtype == 0 && !fd::tuning(fd::kTuneSpconvV1) && cin == 16 && fd::tuning(fd::kTuneF32ResRG) >= 0) {
         // the 16-channel level: resident weights + register accumulators + empty-item skipping (fd_spconv_f32r.hip); "f32_res_rg" = -1
         // keeps the pair-compacting kernel for A/B runs
@@ -355,4 +369,47 @@ extern "C" int fd_spconv_apply_plan(const void *in_feats, int64_t n_in, const vo
     }
     return spconv_apply(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected, cin, cout,
                         dtype, out_feats, stream, plan, plan_stride);
+}
+
+// The layout bits fd_spconv_apply_layout should be given for a layer of this shape inside a level whose inner tensors are ours to lay
+// out (0: plain rows): all three for the SubM layers of a bank-spread level, bit 2 for the strided layer that writes the level's first
+// tensor.  "spconv_swz": -1 none, 0 the levels that measured faster (kSwzDefaultLevels), > 0 a mask of levels (1: the 32-channel level,
+// 2: 64, 4: 128) for A/B runs.  Serial sweeps, layout on against off in one build: the four 32 -> 32 launches 845 -> 837 us,
+// the 64 -> 64 launches 1524 -> 1528 us (nothing), the 128 -> 128 launches 2303 -> 2315 us (slower): only the 32-channel level is on.
+constexpr int kSwzDefaultLevels = 1;
+extern "C" int fd_spconv_layout_wanted(int cin, int cout, int dtype) {
+    const int knob = fd::tuning(fd::kTuneSpconvSwz);
+    if (dtype != 0 || knob < 0 || fd::tuning(fd::kTuneSpconvV1)) return 0;
+    const int levels = knob == 0 ? kSwzDefaultLevels : knob;
+    const int level = cout == 32 ? 1 : cout == 64 ? 2 : cout == 128 ? 4 : 0;
+    if (!(levels & level)) return 0;
+    if (cin == cout) return (cout == 32 && fd::tuning(fd::kTuneSpconvC32) < 0) ? 0 : 7;  // (32 -> 32: only the 32-pair kernel has the gather)
+    return 2 * cin == cout ? 4 : 0;
+}
+
+// fd_spconv_apply_plan with a layout word: which of the launch's tensors are stored bank-spread (fd_spconv_chunk.h: 16-byte piece s of
+// row r at piece s ^ (r & 7) of its 128-byte line) -- bit 0 the input rows, bit 1 the residual, bit 2 the output.  For tensors that only
+// these kernels read, i.e. a level's inner tensors; the values are those of the plain launch bit for bit, only where they sit changes.
+// layout == 0 is fd_spconv_apply_plan.  A shape without an instantiation for the layout is refused (FD_EINVAL), nothing is launched.
+extern "C" int fd_spconv_apply_layout(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
+                                      const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
+                                      const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats,
+                                      const int32_t *plan, int64_t plan_stride, int layout, fd_stream_t stream) {
+    if (layout == 0)
+        return fd_spconv_apply_plan(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected,
+                                    cin, cout, dtype, out_feats, plan, plan_stride, stream);
+    FD_REQUIRE(nbr || plan, "fd_spconv_apply_layout: nbr == NULL needs a chunk plan (fd_spconv_plan_from_index)");
+    if (plan) {
+        FD_REQUIRE(K == fd::kSpconvMaxTaps, "fd_spconv_apply_layout: a chunk plan belongs to an fp32 layer of K = 27 taps");
+        FD_REQUIRE(nbr == nullptr || cin == cout, "fd_spconv_apply_layout: next to a rulebook table a chunk plan belongs to an fp32 SubM layer (K = 27)");
+        FD_REQUIRE(plan_stride >= fd_spconv_plan_stride(n_out), "fd_spconv_apply_layout: plan_stride below fd_spconv_plan_stride(n_out)");
+        if (!nbr) {
+            FD_REQUIRE(fd_spconv_index_plan_wanted(cin, cout, dtype),
+                       "fd_spconv_apply_layout: nbr == NULL, but no kernel runs this layer shape from a chunk plan alone (fd_spconv_index_plan_wanted)");
+        } else if (!fd_spconv_plan_wanted(cin, cout, dtype)) {
+            plan = nullptr;
+        }
+    }
+    return spconv_apply(in_feats, n_in, wpacked, bias, residual, relu, nbr, nbr_stride, ranges, n_ranges, K, n_out, n_out_dev, n_expected, cin, cout,
+                        dtype, out_feats, stream, plan, plan_stride, layout);
 }

@@ -33,7 +33,8 @@ constexpr sk::Layout L = sk::layout(TM, COUT, TS, 32);
 static_assert(((sk::kMaxTaps + TS - 1) / TS) * (TM / WR / 32) <= L.item_slot, "item list slot");
 
 // PLAN: nbr / nbr_stride are a chunk plan (fd_spconv_chunk.h) instead of the rulebook: the lists arrive compacted
-template <int CIN, int DEPTH, bool PLAN>
+// SWZ: the input rows are stored bank-spread (fd_spconv_chunk.h); `relu` carries skeleton::kernel_flags
+template <int CIN, int DEPTH, bool PLAN, bool SWZ>
 __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ in, const float4 *__restrict__ wp, const float *__restrict__ bias,
                                                       const float *__restrict__ residual, int relu, const int *__restrict__ nbr, int64_t nbr_stride,
                                                       int K, int n_out, const int *__restrict__ n_out_dev, float *__restrict__ out, unsigned in_bytes,
@@ -66,9 +67,9 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
         int row0, n_rows;
         if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
         if constexpr (PLAN) {
-            sk::stage_plan_chunk<TM, COUT, TS, 32>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, row0, n_rows);
+            sk::stage_plan_chunk<TM, COUT, TS, 32>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, relu, row0, n_rows);
         } else {
-            sk::stage_chunk<TM, COUT, TS, 32>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
+            sk::stage_chunk<TM, COUT, TS, 32>(pre, s_list, s_pad, s_acc, bias, residual, relu, K, row0, n_rows);
             __syncthreads();
             sk::compact_taps<TM, WR>(s_list, s_cnt, K);
         }
@@ -83,8 +84,15 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
         u32x4 a_r[DEPTH][NCH];
         auto stage_a0 = [&](int it) -> int { return sk::stage_a0(items, n_items, it); };
         auto stage_a1 = [&](int it, int code_v, int &kk, int &e) { sk::stage_a1<TM, WR, 32>(s_list, s_pad, n_items, wr, ln, it, code_v, kk, e); };
-        auto gather_offset = [&](int e) -> unsigned { return sk::entry_row_bytes<CIN>(e) + (unsigned)(lh * 16); };
-        auto gather_step = [&](unsigned voff, int c) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 32, 0, 0); };
+        // bank-spread rows: the lane's piece is lh + 2 c of the row's one line, stored at piece ^ (row & 7): the row's bits go into
+        // the offset once per item, the step's bits with one XOR per load (they no longer add)
+        auto gather_offset = [&](int e) -> unsigned {
+            const unsigned o = sk::entry_row_bytes<CIN>(e) + (unsigned)(lh * 16);
+            return SWZ ? o ^ sk::entry_swz_bits(e) : o;
+        };
+        auto gather_step = [&](unsigned voff, int c) {
+            return SWZ ? __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff ^ (unsigned)(c * 32), 0, 0) : __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 32, 0, 0);
+        };
         float4 b[NCH];  // this tap's weights: channels 8 c + 4 lh .. + 3, output channel ln
         auto load_b = [&](int k) {
             const float4 *wk = wp + (int64_t)k * NCH * 64 + lane;
@@ -157,17 +165,17 @@ __global__ void __launch_bounds__(256) spconv_f32_c32(const float *__restrict__ 
     }
 }
 
-template <int CIN, int DEPTH, bool PLAN>
+template <int CIN, int DEPTH, bool PLAN, bool SWZ>
 int launch_c32(const fd::SpconvCall &c) {
     const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
     int n_ranges = c.n_ranges, rows_per = 0;
     if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its dynamic-LDS limit raised (> 64 KB)
-    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(spconv_f32_c32<CIN, DEPTH, PLAN>), (size_t)L.bytes, lds_set)) return 0;
+    if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(spconv_f32_c32<CIN, DEPTH, PLAN, SWZ>), (size_t)L.bytes, lds_set)) return 0;
     // the 32x32x2 fragment layout ([K][CIN / 8][64 lanes] float4, see fd_spconv_pack_weight)
     const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).c32.offset;
-    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH, PLAN>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, c.stream, (const float *)c.in, (const float4 *)wp,
-                       c.bias, (const float *)c.residual, c.relu, PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
+    hipLaunchKernelGGL((spconv_f32_c32<CIN, DEPTH, PLAN, SWZ>), dim3((unsigned)n_ranges), dim3(256), (size_t)L.bytes, c.stream, (const float *)c.in, (const float4 *)wp,
+                       c.bias, (const float *)c.residual, sk::kernel_flags(c.relu, c.layout), PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev, (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }
 
@@ -178,6 +186,7 @@ namespace fd {
 int spconv_f32_c32_dispatch(const SpconvCall &c) {
     if (c.cout != 32 || c.cin != 32) return 0;
     if (!sk::entries_fit(c.n_in, c.cin)) return 0;
-    return c.plan ? launch_c32<32, 3, true>(c) : launch_c32<32, 3, false>(c);
+    if (c.layout & sk::kLayoutIn) return c.plan ? launch_c32<32, 3, true, true>(c) : launch_c32<32, 3, false, true>(c);
+    return c.plan ? launch_c32<32, 3, true, false>(c) : launch_c32<32, 3, false, false>(c);
 }
 }  // namespace fd

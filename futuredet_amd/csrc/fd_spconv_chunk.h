@@ -38,6 +38,31 @@ __device__ __forceinline__ unsigned entry_row_bytes(int e) {
     const unsigned hi = (unsigned)e & 0xffffff00u;
     return CIN >= 64 ? hi << (CIN == 128 ? 1 : 0) : hi >> (CIN == 32 ? 1 : 2);
 }
+
+// ---------------------------------------------------------------------------------------------- bank-spread row layout
+// A b128 gather is served in passes of 16 lanes, and a pass takes as long as its fullest 16-byte position of a 128-byte line.  The
+// MFMA operand layout puts 16 different rows at ONE channel offset in the lanes of a pass: all 16 on one position.  A tensor that
+// only these kernels read (a level's inner tensors) may therefore be stored bank-spread: 16-byte piece s of row r sits at piece
+// s ^ (r & 7) of its 128-byte line, so the rows of a pass spread over the 8 positions.  Pieces keep their line (256- and 512-byte
+// rows), the positions of one line are a permutation (row-contiguous stores stay row-contiguous), and rows of fewer than 128 bytes
+// (16 channels) are never spread.  The layout word of a launch (fd_spconv_apply_layout) says which of its tensors are stored so:
+constexpr int kLayoutIn = 1, kLayoutResidual = 2, kLayoutOut = 4;
+// The kernels take the residual / output bits in their `relu` word, above the ReLU bit (no further kernel argument); the input bit
+// is a compile-time switch of the gather (SWZ).
+constexpr int kFlagRelu = 1, kFlagResidualSwz = kLayoutResidual, kFlagOutSwz = kLayoutOut;
+constexpr int kernel_flags(int relu, int layout) { return (relu ? kFlagRelu : 0) | (layout & (kLayoutResidual | kLayoutOut)); }
+// byte position of 16-byte piece `s` (0..7) of row `r` within the piece's 128-byte line
+__host__ __device__ constexpr unsigned swz_piece_bytes(unsigned s, unsigned r) { return (s ^ (r & 7u)) << 4; }
+// float4 column c4 of row `row` of a COLS-channel tensor, as stored: `on` = the tensor is bank-spread (wave-uniform)
+template <int COLS>
+__device__ __forceinline__ int swz_col4(int c4, int row, bool on) {
+    if constexpr (COLS < 32) return c4;
+    return c4 ^ (row & (on ? 7 : 0));
+}
+// the row-dependent term of a bank-spread gather offset, from the list entry (bits 8..10 = input row & 7): XORed into the byte offset
+// of the lane's piece once per item.  The padding entry keeps all its high bits: still out of range.
+__device__ __forceinline__ unsigned entry_swz_bits(int e) { return ((unsigned)e >> 4) & 0x70u; }
+
 // host: the entry must fit an int32 and the feature matrix a 31-bit buffer range
 inline bool entries_fit(int64_t n_in_bound, int cin) { return n_in_bound < (1ll << 23) && n_in_bound * cin * 4 < (1ll << 31); }
 
@@ -161,7 +186,7 @@ template <int COUT>
 constexpr bool kInitAcc = COUT <= 64;
 
 template <int TM, int COUT, int TS>
-__device__ __forceinline__ void init_acc(float *s_acc, const float *bias, const float *residual, int row0, int n_rows) {
+__device__ __forceinline__ void init_acc(float *s_acc, const float *bias, const float *residual, int flags, int row0, int n_rows) {
     const int tid = threadIdx.x;
     if constexpr (kInitAcc<COUT>) {
         constexpr int C4i = COUT / 4, NINIT = TM * C4i / 256;
@@ -178,7 +203,7 @@ __device__ __forceinline__ void init_acc(float *s_acc, const float *bias, const 
             for (int i = 0; i < NINIT; ++i) {
                 const int t = tid + i * 256, r = t / C4i, c4 = t - r * C4i;
                 const int rr = r < n_rows ? r : n_rows - 1;  // (clamped address, selected on use)
-                rv[i] = reinterpret_cast<const float4 *>(residual + (int64_t)(row0 + rr) * COUT)[c4];
+                rv[i] = reinterpret_cast<const float4 *>(residual + (int64_t)(row0 + rr) * COUT)[swz_col4<COUT>(c4, row0 + rr, flags & kFlagResidualSwz)];
             }
 #pragma unroll
             for (int i = 0; i < NINIT; ++i) { iv[i].x += rv[i].x; iv[i].y += rv[i].y; iv[i].z += rv[i].z; iv[i].w += rv[i].w; }
@@ -198,7 +223,7 @@ __device__ __forceinline__ void init_acc(float *s_acc, const float *bias, const 
 // stage the prefetched slice (rows past the chunk's end as "no pair"), start the accumulators, write the padding block
 template <int TM, int COUT, int TS, int ITEM>
 __device__ __forceinline__ void stage_chunk(const int (&pre)[kSliceRegs<TM>], int *s_list, int *s_pad, float *s_acc, const float *bias,
-                                            const float *residual, int K, int row0, int n_rows) {
+                                            const float *residual, int flags, int K, int row0, int n_rows) {
     const int tid = threadIdx.x;
     static_assert(256 % TM == 0, "a thread stages the same local row in every pass");
     const bool in_chunk = tid % TM < n_rows;
@@ -207,7 +232,7 @@ __device__ __forceinline__ void stage_chunk(const int (&pre)[kSliceRegs<TM>], in
         const int t = tid + i * 256;
         if (t < K * TM) s_list[t] = in_chunk ? pre[i] : -1;
     }
-    init_acc<TM, COUT, TS>(s_acc, bias, residual, row0, n_rows);
+    init_acc<TM, COUT, TS>(s_acc, bias, residual, flags, row0, n_rows);
     if (tid < ITEM) s_pad[tid] = pad_entry(TM);
 }
 
@@ -231,7 +256,7 @@ inline int64_t plan_stride_for(int64_t n_out) { return (n_out + 8 + 63) / 64 * 6
 // (positions past the chunk's rows belong to the next chunk: padding), the counts are unpacked; no compaction pass follows.
 template <int TM, int COUT, int TS, int ITEM>
 __device__ __forceinline__ void stage_plan_chunk(const int (&pre)[kSliceRegs<TM>], int *s_list, unsigned char *s_cnt, int *s_pad, float *s_acc,
-                                                 const float *bias, const float *residual, int row0, int n_rows) {
+                                                 const float *bias, const float *residual, int flags, int row0, int n_rows) {
     const int tid = threadIdx.x;
     static_assert(TM == kPlanTM && 256 % TM == 0, "the plan is cut for 128-row chunks");
     static_assert(kSliceRegs<TM> * 256 >= kMaxTaps * TM + kPlanCountWords, "the count words ride in the slice's last register");
@@ -248,7 +273,7 @@ __device__ __forceinline__ void stage_plan_chunk(const int (&pre)[kSliceRegs<TM>
                 if (k0 + q < kMaxTaps) s_cnt[(k0 + q) * 4] = (unsigned char)((unsigned)pre[i] >> (8 * q));
         }
     }
-    init_acc<TM, COUT, TS>(s_acc, bias, residual, row0, n_rows);
+    init_acc<TM, COUT, TS>(s_acc, bias, residual, flags, row0, n_rows);
     if (tid < ITEM) s_pad[tid] = pad_entry(TM);
 }
 
@@ -327,7 +352,8 @@ __device__ __forceinline__ void stage_a1(const int *s_list, const int *s_pad, in
 // -------------------------------------------------------------------------------------------------------- epilogue
 // whole chunk, float4 per thread, rows contiguous in global memory (swizzled slots in LDS)
 template <int TM, int COUT, int TS>
-__device__ __forceinline__ void epilogue(float *s_acc, const float *bias, const float *residual, int relu,
+// `flags`: kFlagRelu, and whether `residual` / `out` are stored bank-spread
+__device__ __forceinline__ void epilogue(float *s_acc, const float *bias, const float *residual, int flags,
                                          float *out, int row0, int n_rows) {
     const int tid = threadIdx.x;
     constexpr int C4 = COUT / 4;
@@ -347,12 +373,12 @@ __device__ __forceinline__ void epilogue(float *s_acc, const float *bias, const 
                 v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
             }
             if (residual) {
-                const float4 rv = reinterpret_cast<const float4 *>(residual + (int64_t)row * COUT)[c4];
+                const float4 rv = reinterpret_cast<const float4 *>(residual + (int64_t)row * COUT)[swz_col4<COUT>(c4, row, flags & kFlagResidualSwz)];
                 v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
             }
         }
-        if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        reinterpret_cast<float4 *>(out + (int64_t)row * COUT)[c4] = v;
+        if (flags & kFlagRelu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        reinterpret_cast<float4 *>(out + (int64_t)row * COUT)[swz_col4<COUT>(c4, row, flags & kFlagOutSwz)] = v;
     }
 }
 

@@ -70,7 +70,8 @@ __device__ unsigned long long *g_trace;
 constexpr int tap_splits(int cout) { return (cout == 32 || cout == 64) ? 2 : 1; }
 
 // PLAN: nbr / nbr_stride are a chunk plan (fd_spconv_chunk.h) instead of the rulebook: the lists arrive compacted
-template <int CIN, int COUT, int TM, int DEPTH, bool PLAN>
+// SWZ: the input rows are stored bank-spread (fd_spconv_chunk.h); `relu` carries skeleton::kernel_flags
+template <int CIN, int COUT, int TM, int DEPTH, bool PLAN, bool SWZ>
 __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restrict__ in, const float4 *__restrict__ wp,
                                                           const float *__restrict__ bias, const float *__restrict__ residual, int relu,
                                                           const int *__restrict__ nbr, int64_t nbr_stride, int K, int n_out,
@@ -84,6 +85,7 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     constexpr int NACC = NBW;  // one accumulator chain per column block (dependent 16x16x4 MFMAs issue back to back at full rate)
     static_assert((TM == 128 || TM == 64) && TM / WR >= 16, "local row uses 8 bits (0..TM, TM = scratch row)");
     static_assert(!PLAN || (TM == sk::kPlanTM && WR == 1), "the chunk plan holds the lists of 128-row chunks with one row set");
+    static_assert(!SWZ || CIN >= 32, "rows of fewer than 128 bytes are never bank-spread");
     constexpr int kPad = sk::pad_entry(TM);
     constexpr sk::Layout L = sk::layout(TM, COUT, TS, 16);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -115,9 +117,9 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     int row0, n_rows;
     if (!sk::chunk_span(r_begin, r_end, chunk_rows, chunk, row0, n_rows)) break;
     if constexpr (PLAN) {
-        sk::stage_plan_chunk<TM, COUT, TS, 16>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, row0, n_rows);
+        sk::stage_plan_chunk<TM, COUT, TS, 16>(pre, s_list, s_cnt, s_pad, s_acc, bias, residual, relu, row0, n_rows);
     } else {
-        sk::stage_chunk<TM, COUT, TS, 16>(pre, s_list, s_pad, s_acc, bias, residual, K, row0, n_rows);
+        sk::stage_chunk<TM, COUT, TS, 16>(pre, s_list, s_pad, s_acc, bias, residual, relu, K, row0, n_rows);
         __syncthreads();
         if (chunk == 0) FD_T(1);
         sk::compact_taps<TM, WR>(s_list, s_cnt, K);
@@ -152,8 +154,17 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     // fixed order (taps ascending): deterministic.
     auto stage_a0 = [&](int it) -> int { return sk::stage_a0(items, n_items, it); };
     auto stage_a1 = [&](int it, int code_v, int &kk, int &e) { sk::stage_a1<TM, WR, 16>(s_list, s_pad, n_items, wr, lrow, it, code_v, kk, e); };
-    auto gather_offset = [&](int e) -> unsigned { return sk::entry_row_bytes<CIN>(e) + (unsigned)(lq * 16); };
-    auto gather_chunk = [&](unsigned voff, int c) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 64, 0, 0); };
+    // bank-spread rows: the lane's piece of 16-channel chunk c is lq + 4 (c & 1) of line c / 2, stored at piece ^ (row & 7).  The
+    // row's bits go into the offset once per item; the odd chunks read from that offset ^ 64 (one XOR per item, which the compiler
+    // shares between them), and the line stays an immediate
+    auto gather_offset = [&](int e) -> unsigned {
+        const unsigned o = sk::entry_row_bytes<CIN>(e) + (unsigned)(lq * 16);
+        return SWZ ? o ^ sk::entry_swz_bits(e) : o;
+    };
+    auto gather_chunk = [&](unsigned voff, int c) {
+        return SWZ ? __builtin_amdgcn_raw_buffer_load_b128(rsrc, (voff ^ (unsigned)((c & 1) * 64)) + (c >> 1) * 128, 0, 0)
+                   : __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 64, 0, 0);
+    };
     auto load_b = [&](int k, float4(&dst)[NC][NBW]) {
         const float4 *wk = wp + ((int64_t)k * NC * NB + wc * NBW) * 64 + lane;
 #pragma unroll
@@ -286,23 +297,34 @@ inline size_t lds_request(int cin, int cout, int tm) {
     return (cin == 64 && cout == 64 && tm == 128 && lds < 56 * 1024) ? (size_t)56 * 1024 : lds;
 }
 
-template <int CIN, int COUT, int TM, int DEPTH, bool PLAN = false>
+// the shapes with a bank-spread gather: 64 -> 64 and 128 -> 128 (32 -> 32 has its own kernel, fd_spconv_c32.hip)
+constexpr bool has_swz_gather(int cin, int cout, int tm) { return cin == cout && (cin == 64 || cin == 128) && tm == sk::kPlanTM; }
+
+template <int CIN, int COUT, int TM, int DEPTH, bool PLAN = false, bool SWZ = false>
 int launch_compact(const fd::SpconvCall &c) {
+    if constexpr (!PLAN && !SWZ) {
+        // a bank-spread tensor: the input only where the gather is instantiated, output / residual rows of 128 bytes and more
+        if ((c.layout & sk::kLayoutIn) && !has_swz_gather(CIN, COUT, TM)) return 0;
+        if ((c.layout & (sk::kLayoutResidual | sk::kLayoutOut)) && COUT < 32) return 0;
+        if constexpr (has_swz_gather(CIN, COUT, TM)) {
+            if (c.layout & sk::kLayoutIn) return launch_compact<CIN, COUT, TM, DEPTH, false, true>(c);
+        }
+    }
     // the layers that read a chunk plan: SubM at 32 channels and up, and the strided 16 -> 32, 32 -> 64, 64 -> 128 (one row set per
     // 128-row chunk each)
     if constexpr (!PLAN && ((CIN == COUT && COUT >= 32) || COUT == 2 * CIN) && TM == sk::kPlanTM) {
-        if (c.plan) return launch_compact<CIN, COUT, TM, DEPTH, true>(c);
+        if (c.plan) return launch_compact<CIN, COUT, TM, DEPTH, true, SWZ>(c);
     }
     const size_t lds_req = lds_request(CIN, COUT, TM);
     static std::atomic<uint64_t> lds_set{0};  // devices on which this instantiation has its LDS limit raised
-    auto kern = spconv_f32_compact<CIN, COUT, TM, DEPTH, PLAN>;
+    auto kern = spconv_f32_compact<CIN, COUT, TM, DEPTH, PLAN, SWZ>;
     if (!fd::ensure_dynamic_lds(reinterpret_cast<const void *>(kern), lds_req, lds_set)) return 0;
     const unsigned in_bytes = (unsigned)(c.n_in * CIN * 4);
     int n_ranges = c.n_ranges, rows_per = 0;
     if (!c.ranges) sk::equal_rows_split(c.n_out, TM, c.n_out_dev != nullptr, n_ranges, rows_per);
     const void *wp = (const char *)c.wpacked + fd::spconv_weight_layout(c).base.offset;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_ranges), dim3(256), lds_req, c.stream, (const float *)c.in, (const float4 *)wp, c.bias,
-                       (const float *)c.residual, c.relu, PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev,
+                       (const float *)c.residual, sk::kernel_flags(c.relu, c.layout), PLAN ? c.plan : c.nbr, PLAN ? c.plan_stride : c.nbr_stride, c.K, c.n_out, c.n_out_dev,
                        (float *)c.out, in_bytes, c.ranges, rows_per);
     return 1;
 }

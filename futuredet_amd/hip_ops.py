@@ -214,6 +214,29 @@ def index_plan_wanted(src, dst, ksize, cin, cout):
             and bool(_lib.load().fd_spconv_index_plan_wanted(int(cin), int(cout), 0)))
 
 
+def swizzle_rows(t):
+    """The bank-spread layout of fd_spconv_apply_layout, stated in torch: 16-byte piece s of row r of an fp32 [n, c] tensor at piece
+    s ^ (r & 7) of its 128-byte line; rows of fewer than 32 channels stay as they are.  Its own inverse.  (Tests and tools: the
+    kernels read and write the layout themselves.)"""
+    n, c = t.shape
+    if c < 32 or n == 0:
+        return t.clone()
+    assert t.dtype == torch.float32 and c % 32 == 0
+    r = torch.arange(n, device=t.device) & 7
+    idx = torch.arange(8, device=t.device)[None, :] ^ r[:, None]
+    return torch.gather(t.reshape(n, c // 32, 8, 4), 2, idx[:, None, :, None].expand(n, c // 32, 8, 4)).reshape(n, c)
+
+
+def level_layout(cin, cout, n_in, n_out):
+    """True when the inner tensors of a sparse level -- strided cin -> cout convolution from n_in to n_out rows, then cout -> cout SubM
+    layers -- are to be stored bank-spread (fd_spconv_layout_wanted; fp32, row counts within the 32-bit gather offsets of the kernels
+    that read such rows: the launches of a larger level fall back to kernels that only know plain rows)."""
+    L = _lib.load()
+    fits = lambda n, c: 0 < n < (1 << 23) and n * c * 4 < (1 << 31)  # noqa: E731
+    return bool(fits(n_in, cin) and fits(n_out, cout) and L.fd_spconv_layout_wanted(int(cout), int(cout), 0) == 7
+                and L.fd_spconv_layout_wanted(int(cin), int(cout), 0) & 4)
+
+
 class IndexRulebook(object):
     """Stands where the K = 27 table of SparseIndex.rulebook would on the fp32 inference sweep: the two indexes and the window, from
     which plans_from_index / ranges_for write the chunk plans and the equal-work ranges that the kernels read.  Carries the table's
@@ -560,7 +583,8 @@ def dense_gather(grad, index, c):
     return feats
 
 
-def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=False, out=None, balanced=None, plan=None):
+def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=False, out=None, balanced=None, plan=None, layout=0):
+    """``layout``: which tensors are stored bank-spread (fd_spconv_apply_layout: 1 the input rows, 2 the residual, 4 the output)."""
     L = _lib.load()
     feats = _dev(feats, "feats")
     dt = _DT[feats.dtype]
@@ -581,6 +605,13 @@ def spconv_apply(feats, wpacked, bias, nbr, n_out, cout, residual=None, relu=Fal
     # An IndexRulebook has no table at all: its plan comes straight from the index, for the strided 16 -> 32 ... 64 -> 128 layers too.
     if plan is None:
         plan = from_index or (dt == 0 and n_out > 0 and K == 27 and cin == cout and bool(L.fd_spconv_plan_wanted(cin, cout, 0)))
+    if layout:
+        plan_t, pstride = plan_for(nbr if from_index else _dev(nbr, "nbr", torch.int32), n_out, ranges, n_ranges) if plan else (None, 0)
+        check(L.fd_spconv_apply_layout(_p(feats), feats.shape[0], _p(_dev(wpacked, "wpacked")), _p(bias), _p(residual), int(bool(relu)),
+                                       None if from_index else _p(_dev(nbr, "nbr", torch.int32)), nstride, _p(ranges), n_ranges, K, n_out,
+                                       _p(n_dev), int(n_expected or 0), cin, cout, dt, _p(out), _p(plan_t), pstride, int(layout), _stream()),
+              "fd_spconv_apply_layout")
+        return out
     if plan:
         plan_t, pstride = plan_for(nbr if from_index else _dev(nbr, "nbr", torch.int32), n_out, ranges, n_ranges)
         check(L.fd_spconv_apply_plan(_p(feats), feats.shape[0], _p(_dev(wpacked, "wpacked")), _p(bias), _p(residual), int(bool(relu)),

@@ -124,6 +124,9 @@ SIGNATURES = {
     "fd_spconv_apply_plan": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_i64,
                                      c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     "fd_spconv_index_plan_wanted": (c_int, [c_int, c_int, c_int]),
+    "fd_spconv_layout_wanted": (c_int, [c_int, c_int, c_int]),
+    "fd_spconv_apply_layout": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_int, c_int, c_i64,
+                                       c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
     "fd_spconv_plan_from_index": (c_int, [c_int, c_int, ctypes.POINTER(PlanSource), c_void_p]),
     "fd_spconv_ranges_from_index": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                             c_void_p]),

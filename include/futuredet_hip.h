@@ -38,7 +38,8 @@ const char *fd_last_error(void);
  * the 16-pair compacting kernel instead of the 32-pair one), "v2_ranges_per_cu" (row ranges per compute unit of the compacting
  * kernels), "f32_res_rg" (-1: 16-channel fp32 layers on the pair-compacting kernel instead of the resident-weights one; 2: two row
  * groups per wave; 32: 16 -> 32 on it as well), "f32_res_nw" (1: that kernel on XCD-contiguous tile chunks instead of interleaved
- * tiles), "spconv_plan" (-1: fd_spconv_apply_plan ignores the chunk plan), "bf16_gp" (-1: bf16 on the register kernel), "bf16_rg" / "bf16_depth" (row groups per wave / gather-ring depth of the bf16
+ * tiles), "spconv_plan" (-1: fd_spconv_apply_plan ignores the chunk plan), "spconv_swz" (-1: fd_spconv_layout_wanted answers 0, no bank-spread rows),
+ * "bf16_gp" (-1: bf16 on the register kernel), "bf16_rg" / "bf16_depth" (row groups per wave / gather-ring depth of the bf16
  * kernels), "bf16_win" (-1: the 64 -> 64 / 128 -> 128 bf16 layers on the RING / RESIDENT kernels instead of the LDS-window
  * kernel), "bf16_nw" (1: RESIDENT bf16 kernels walk XCD-contiguous tile chunks instead of tiles interleaved over the grid),
  * "conv_nt" (output channels per workgroup of the bf16 dense conv: 64 | 32), "conv_strip" (1: stride-1 bf16 dense layers on strips
@@ -191,6 +192,20 @@ typedef struct fd_plan_source {
     int32_t stride[3], pad[3];
 } fd_plan_source;
 int fd_spconv_index_plan_wanted(int cin, int cout, int dtype);
+/* Bank-spread rows between two of our own kernels.  fd_spconv_apply_layout is fd_spconv_apply_plan plus a layout word that says which
+ * of the launch's tensors are stored with 16-byte piece s of row r at piece s ^ (r & 7) of its 128-byte line (pieces keep their line
+ * in 256- and 512-byte rows; 64-byte rows are never spread): bit 0 the input rows, bit 1 the residual, bit 2 the output.  The values
+ * are those of the plain launch bit for bit; a gather of 16 different rows at one channel offset then spreads over the 8 positions
+ * of a line instead of queueing on one.  For tensors nothing else reads: a level's inner tensors.  layout == 0 is
+ * fd_spconv_apply_plan.  fp32 only: all bits for 32 -> 32, 64 -> 64 and 128 -> 128, bits 1 and 2 for every shape of 32 output channels
+ * and up on the pair-compacting kernels; any other launch is FD_EINVAL and launches nothing.  fd_spconv_layout_wanted: the bits a layer
+ * of this shape should get inside such a level (SubM layers 7, the strided layer into the level 4, else 0), 0 under
+ * fd_tuning_set("spconv_swz", -1); a positive "spconv_swz" is a mask of levels for A/B runs (1: 32 channels, 2: 64, 4: 128). */
+int fd_spconv_layout_wanted(int cin, int cout, int dtype);
+int fd_spconv_apply_layout(const void *in_feats, int64_t n_in, const void *wpacked, const float *bias, const void *residual, int relu,
+                           const int32_t *nbr, int64_t nbr_stride, const int32_t *ranges, int n_ranges, int K, int64_t n_out,
+                           const int32_t *n_out_dev, int64_t n_expected, int cin, int cout, int dtype, void *out_feats,
+                           const int32_t *plan, int64_t plan_stride, int layout, fd_stream_t stream);
 int fd_spconv_plan_from_index(int B, int n_sources, const fd_plan_source *sources_host, fd_stream_t stream);
 int fd_spconv_ranges_from_index(const uint64_t *words, int B, int D, int H, int W, const int32_t *coords, int64_t n_out,
                                 const int32_t *n_out_dev, int n_ranges, int32_t *ranges /*[n_ranges+1]*/, void *workspace,

@@ -13,6 +13,15 @@
 //   11 mfma256_half_oob  as 6, odd rows out of range;  12 mfma256_half_masked  as 6, odd rows' lanes switched off
 //   13 mfma_quarter_masked  as 2, three of four rows' lanes switched off
 //   7 blocked    lane p+16q -> (r0 + p) * 16 + q * 256 within a 1 KB block: chunk-major blocked layout, consecutive rows
+// Patterns 14 and up are the gathers of the sparse-convolution kernels themselves, instruction for instruction: consecutive
+// instructions of a wave are the channel steps of one item (the same rows), then the next item's rows follow.
+//   v2_<B>     fd_spconv_v2.hip at row size B = 128 / 256 / 512 bytes (CIN 32 / 64 / 128): 16 rows per item, B / 64 instructions,
+//              lane p+16q of step c -> row(p) * B + 16 (q + 4 c)
+//   c32        fd_spconv_c32.hip: 32 rows of 128 bytes per item, 4 instructions, lane n+32h of step c -> row(n) * 128 + 16 (h + 2 c)
+//   quad128    lane 8p+q -> row(p) * 128 + 16 q, 8 rows per instruction: every lane group reads whole lines (the upper mark)
+//   ..._swz    the same lanes and channels, the 16-byte piece s of a row stored at piece s ^ (row & 7) of its 128-byte line
+//   ..._near   rows ascending with gaps of 1 or 2 (a tap's list of a sorted cloud) instead of random rows of the window
+// usage: gather_probe [waves per CU = 16] [first pattern = 0]
 // build: hipcc --offload-arch=gfx950 -O3 -o tools/probes/gather_probe tools/probes/gather_probe.hip
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -52,8 +61,33 @@ __global__ void __launch_bounds__(1024) probe(const unsigned char *buf, unsigned
     if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) sink[0] = 1;
 }
 
+// the kernels' own patterns (14 and up)
+struct KernelPattern {
+    const char *name;
+    int kind;  // 0 v2, 1 c32, 2 quad128
+    unsigned row_bytes;
+    bool swz, near;
+};
+static const KernelPattern kKernelPatterns[] = {
+    {"v2_128", 0, 128, false, false},      {"v2_128_swz", 0, 128, true, false},      {"v2_256", 0, 256, false, false},
+    {"v2_256_swz", 0, 256, true, false},   {"v2_512", 0, 512, false, false},         {"v2_512_swz", 0, 512, true, false},
+    {"c32", 1, 128, false, false},         {"c32_swz", 1, 128, true, false},         {"quad128", 2, 128, false, false},
+    {"v2_128_near", 0, 128, false, true},  {"v2_128_swz_near", 0, 128, true, true},  {"v2_256_near", 0, 256, false, true},
+    {"v2_256_swz_near", 0, 256, true, true}, {"v2_512_near", 0, 512, false, true},   {"v2_512_swz_near", 0, 512, true, true},
+    {"c32_near", 1, 128, false, true},     {"c32_swz_near", 1, 128, true, true},     {"quad128_near", 2, 128, false, true},
+};
+constexpr int kFirstKernelPattern = 14;
+constexpr int kNumKernelPatterns = (int)(sizeof(kKernelPatterns) / sizeof(kKernelPatterns[0]));
+
+// byte offset of 16-byte piece `piece` of row `row`: plain, or XOR-swizzled within the piece's 128-byte line
+static unsigned piece_offset(unsigned row, unsigned row_bytes, unsigned piece, bool swz) {
+    const unsigned line = piece >> 3, s = piece & 7;
+    return row * row_bytes + line * 128 + ((swz ? s ^ (row & 7) : s) << 4);
+}
+
 int main(int argc, char **argv) {
     const int waves_per_cu = argc > 1 ? atoi(argv[1]) : 16;
+    const int first_pat = argc > 2 ? atoi(argv[2]) : 0;
     const int reps = 64, UNROLL = 8;
     hipDeviceProp_t prop;
     hipGetDeviceProperties(&prop, 0);
@@ -78,12 +112,34 @@ int main(int argc, char **argv) {
     const size_t windows[] = {16u << 10, 2u << 20, 24u << 20};
     printf("%d CUs, %d waves per CU, %d loads of 1 KB per wave\n", n_cu, waves_per_cu, reps * UNROLL);
     for (size_t win : windows) {
-        for (int pat = 0; pat < 14; ++pat) {
+        for (int pat = first_pat; pat < kFirstKernelPattern + kNumKernelPatterns; ++pat) {
+            const KernelPattern *kp = pat >= kFirstKernelPattern ? &kKernelPatterns[pat - kFirstKernelPattern] : nullptr;
             // each CU's waves work in their own window slice when the window is small (L1 case), else share the whole window
             srand(1234 + pat);
             for (int w = 0; w < n_waves; ++w) {
                 const size_t base = win <= (64u << 10) ? ((size_t)(w / wg_waves) * win) % (max_bytes - win) : 0;
-                for (int i = 0; i < reps * UNROLL; ++i) {
+                unsigned item_rows[32];
+                for (int i = 0; kp && i < reps * UNROLL; ++i) {
+                    const int per_item = kp->kind == 0 ? (int)kp->row_bytes / 64 : kp->kind == 1 ? 4 : 1;
+                    const int n_item_rows = kp->kind == 0 ? 16 : kp->kind == 1 ? 32 : 8;
+                    const int c = i % per_item;
+                    const unsigned nrows = (unsigned)(win / kp->row_bytes);
+                    if (c == 0) {
+                        unsigned r = (unsigned)rand() % nrows;
+                        for (int p = 0; p < n_item_rows; ++p) {
+                            item_rows[p] = kp->near ? r % nrows : (unsigned)rand() % nrows;
+                            r += 1 + (unsigned)(rand() & 1);
+                        }
+                    }
+                    for (int l = 0; l < 64; ++l) {
+                        unsigned off;
+                        if (kp->kind == 0) off = piece_offset(item_rows[l & 15], kp->row_bytes, (unsigned)((l >> 4) + 4 * c), kp->swz);
+                        else if (kp->kind == 1) off = piece_offset(item_rows[l & 31], 128, (unsigned)((l >> 5) + 2 * c), kp->swz);
+                        else off = piece_offset(item_rows[l >> 3], 128, (unsigned)(l & 7), kp->swz);
+                        h[((size_t)w * reps * UNROLL + i) * 64 + l] = (unsigned)base + off;
+                    }
+                }
+                for (int i = 0; !kp && i < reps * UNROLL; ++i) {
                     unsigned rows[16];
                     const unsigned rb = (pat == 6 || pat == 11 || pat == 12) ? 256 : 64;
                     const unsigned nrows = (unsigned)(win / rb);
@@ -130,7 +186,7 @@ int main(int argc, char **argv) {
             mean /= n_waves;
             const double kb = (double)reps * UNROLL;  // KB per wave
             const double frac = (pat == 4 || pat == 5 || pat == 10 || pat == 11 || pat == 12) ? 0.5 : (pat == 8 ? 0.0 : (pat == 9 ? 1.0 / 64 : (pat == 13 ? 0.25 : 1.0)));
-            printf("window %7.1f MB  %-10s  %7.1f cycles per 1-KB load per wave  -> %6.1f B/clk/CU (requested %s)  kernel %.1f us  %.2f TB/s\n", win / 1048576.0, names[pat],
+            printf("window %7.1f MB  %-16s  %7.1f cycles per 1-KB load per wave  -> %6.1f B/clk/CU (requested %s)  kernel %.1f us  %.2f TB/s\n", win / 1048576.0, kp ? kp->name : names[pat],
                    mean / kb, 1024.0 * frac * waves_per_cu / (mean / kb), frac < 1 ? "half" : "all", ms * 1e3,
                    (double)n_waves * kb * 1024 * frac / (ms * 1e-3) / 1e12);
         }

@@ -1,6 +1,7 @@
 """Micro-benchmark of fd_spconv_apply on the real rulebooks of one synthetic cloud (for rocprofv3 / tuning).
 usage: python tools/spconv_bench.py [--levels 0,1,2,3] [--dtype fp32] [--iters 20] [--points 300000] [--modes tiles,uniform,balanced]
-       [--rpc 0,1,2]   (ranges per CU override; 0 = library default)"""
+       [--rpc 0,1,2]   (ranges per CU override; 0 = library default)
+       [--layout 0,7]  (fp32: fd_spconv_apply_layout words, each timed and compared with the plain launch; mode "auto" = run_fused's split)"""
 import argparse
 import os
 import sys
@@ -19,6 +20,8 @@ ap.add_argument("--points", type=int, default=300000)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--modes", default="tiles,uniform,balanced")
 ap.add_argument("--rpc", default="0")
+ap.add_argument("--layout", default="0", help="fp32: comma list of layout words (1 input, 2 residual, 4 output rows bank-spread)")
+ap.add_argument("--rounds", type=int, default=1, help="repeat the whole timing this many times")
 ap.add_argument("--gp", default="0", help="bf16: comma list of bf16_gp knob values (0 = gather-pipeline kernel, -1 = the older kernels)")
 ap.add_argument("--rg", default="0", help="bf16 gather pipeline: comma list of row groups per wave (0 = heuristic)")
 ap.add_argument("--bdepth", default="0", help="bf16 gather pipeline: comma list of ring depths (0 = heuristic)")
@@ -34,7 +37,8 @@ bb = build_backbone(dict(type="SpMiddleResNetFHD", num_input_features=5, ds_fact
 bb.load_state_dict(seeded_state_dict(bb, 7), strict=False)
 bb = bb.to(dev).eval()
 idx = bb.build_indexes(lambda i0: i0.mark(out["coors"][:m].contiguous()), 1, [1440, 1440, 40], dev)
-MODE = {"tiles": "tiles", "uniform": False, "balanced": True}
+MODE = {"tiles": "tiles", "uniform": False, "balanced": True, "auto": None}
+layouts = [int(v) for v in args.layout.split(",")] if args.dtype == "fp32" else [0]
 for lvl in [int(v) for v in args.levels.split(",")]:
     C = [16, 32, 64, 128][lvl]
     ix = idx[lvl]
@@ -72,6 +76,23 @@ for lvl in [int(v) for v in args.levels.split(",")]:
                 for other in ref.values():  # two bf16 kernel families: same data, different summation trees
                     assert float((other.float() - y.float()).abs().max()) <= 2e-2 * float(other.float().abs().max()), "bf16 kernels disagree"
             assert torch.equal(ref[key], y), "work distribution changed the result"
+            xs = hip_ops.swizzle_rows(x) if layouts != [0] else None
+            for rnd in range(args.rounds if layouts != [0] else 0):
+                for lay in layouts:
+                    xi, xr = (xs if lay & 1 else x), (xs if lay & 2 else x)
+                    for _ in range(3):
+                        y = hip_ops.spconv_apply(xi, wpk, bias, nbr, ix.n, C, residual=xr, relu=True, balanced=MODE[mode], layout=lay)
+                    assert torch.equal(ref[key], hip_ops.swizzle_rows(y) if lay & 4 else y), "the layout changed the result"
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(args.iters):
+                        y = hip_ops.spconv_apply(xi, wpk, bias, nbr, ix.n, C, residual=xr, relu=True, balanced=MODE[mode], layout=lay)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    print("level %d C=%3d n=%6d pairs=%7d %-8s round %d layout %d: %7.1f us" %
+                          (lvl, C, ix.n, pairs, mode, rnd, lay, 1e3 * e0.elapsed_time(e1) / args.iters), flush=True)
+            if layouts != [0]:
+                continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(args.iters):
