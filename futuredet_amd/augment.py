@@ -11,10 +11,26 @@ preprocess.py:75-90, 212: two cv2.warpAffine calls, restated in the header) and 
                                                                # batch, warps the map and filters the ground truth by the voxel range
     batch = filter_gt_outside_range(aug(batch), cfg.voxel_generator["range"])   # or: a new batch dict for train_steps
 
-Everything is opt-in: with ``warp_bev=False`` / ``filter_gt=False`` the launches are the earlier ones.  In eval mode ``get_mask`` runs
-with identity parameters, under which the warp returns its input bit for bit, so that path needs no code.  Not covered
-(NotImplementedError where a config asks for it): GT-database sampling, ``min_points_in_gt``, ``npoints``; not built: the registered
-``Preprocess`` pipeline stage, which stays a stub, and its name-based class filtering (host-side data preparation).
+GT-database sampling ("GT-AUG", the stage's ``db_sampler``: preprocess.py:147-182, DataBaseSamplerV2.sample_all,
+det3d/core/sampler/sample_ops.py:101-253) runs before those transforms, as in the reference (fd_gt_sample.hip; the header has the
+definition):
+
+    db = GTDatabase.from_dbinfos(cfg.db_sampler["db_info_path"], root, class_names, 5, db_prep_steps=cfg.db_sampler["db_prep_steps"])
+    sampler = GTSampler(db, cfg.db_sampler["sample_groups"], rate=cfg.db_sampler["rate"], sampler_type=cfg.sampler_type, seed=0)
+    aug = GlobalAugment(cfg.train_preprocessor, seed=0, sampler=sampler)      # accepts db_sampler.enable = True
+
+The host draws the database entries (GTSampler: one BatchSampler restatement per group pool); one launch per batch decides on the
+device which of them collide with the sample's ground truth or with one another and appends the accepted entries' rows; one launch per
+cloud pastes their points in front of the scene.  A cloud always grows by ``sampler.point_cap`` rows -- what is not an entry's point
+is a sentinel row far outside every range, which the voxelisers drop -- so the host knows every size and nothing waits for the device.
+GTSampler's docstring names the two intended differences from the reference.
+
+Everything is opt-in: with ``warp_bev=False`` / ``filter_gt=False`` / ``sampler=None`` the launches are the earlier ones.  In eval mode
+``get_mask`` runs with identity parameters, under which the warp returns its input bit for bit, so that path needs no code.  Not
+covered (NotImplementedError where a config asks for it): ``min_points_in_gt``, ``npoints``, per-object rotation noise of the sampler
+(``global_random_rotation_range_per_object`` other than [0, 0]) and group sampling; not built: the registered ``Preprocess`` pipeline
+stage, which stays a stub, its name-based class filtering (host-side data preparation), and the reference's global ``np.random``
+stream (every object here draws from a Generator of its own).
 """
 import collections
 import threading
@@ -72,19 +88,32 @@ class GlobalAugment(object):
     ``draw(B)`` draws B samples' parameters from the object's own ``numpy.random.Generator`` (``seed``) in the reference's order of
     draws -- the reference's global ``np.random`` stream is not reproduced; ``record(params)`` turns them into the kernels' records;
     ``aug(batch)`` returns an augmented copy of a device batch.  With ``no_augmentation=True`` or a mode other than "train" the
-    transforms are the identity and only the shuffle remains.  An enabled ``db_sampler``, ``min_points_in_gt > 0`` and ``npoints > 0``
-    raise NotImplementedError.
+    transforms are the identity and only the shuffle remains.  ``min_points_in_gt > 0`` and ``npoints > 0`` raise NotImplementedError,
+    and so does an enabled ``db_sampler`` unless a ``sampler`` is given.
+
+    ``sampler`` (a GTSampler; None = no GT-database sampling, the launches of before): ``aug(batch)`` first samples -- the candidates
+    are ``batch["gt_sample_candidates"]`` [B, K] if present, else a draw, and are kept in the returned batch -- so the accepted
+    entries' rows join ``gt_boxes`` / ``gt_classes`` / ``gt_trajectory`` below the new ``gt_counts`` (the padded axis must have room
+    for them: a row that does not fit is a rejected candidate and a bit of ``gt_sample_status``), then transforms the boxes with the
+    new counts and builds every cloud as ``augment_points([sampled slots ; scene], perm(n + point_cap))``: each cloud grows by
+    exactly ``sampler.point_cap`` rows, the accepted entries' points and sentinel rows (1e30, 1e30, 1e30, 0[, 0]) that every
+    voxeliser drops as out of range.  ``gt_sample_status`` [B] (the hip_ops.GT_SAMPLE_* bits), ``gt_sample_accepted`` [B, K] and
+    ``gt_sample_points`` [B] stay on the device.
 
     ``warp_bev`` (False = as before): the mask of a bev_map head is warped with the same parameters (the reference's ``get_mask``):
     ``mask_record(params)`` builds fd_augment_mask's records, ``aug(batch)`` also returns a warped copy of ``batch["bev_map"]`` when the
     batch has one, and the static steps draw for such a head and warp the batch's unwarped map themselves.  The map must be
     [B, C, 180, 180] (ValueError otherwise): the reference hard-codes that size and the centre (90, 90)."""
 
-    def __init__(self, cfg, seed=None, warp_bev=False):
+    def __init__(self, cfg, seed=None, warp_bev=False, sampler=None):
         self.warp_bev = bool(warp_bev)
+        self.sampler = sampler
         db = _get(cfg, "db_sampler")
         if db is not None and _get(db, "enable", True):
-            raise NotImplementedError("GlobalAugment: db_sampler (GT-database sampling) is not built; set db_sampler.enable = False")
+            if sampler is None:
+                raise NotImplementedError("GlobalAugment: an enabled db_sampler (GT-database sampling) needs sampler=GTSampler(...); "
+                                          "without one, set db_sampler.enable = False")
+            check_db_sampler_cfg(db)
         if _get(cfg, "min_points_in_gt", -1) > 0:
             raise NotImplementedError("GlobalAugment: min_points_in_gt > 0 (the point-count filter) is not built")
         if _get(cfg, "npoints", -1) > 0:
@@ -100,6 +129,7 @@ class GlobalAugment(object):
         if len(rot) != 2 or len(scale) != 2 or len(std) != 3:
             raise ValueError("GlobalAugment: global_rot_noise / global_scale_noise take two values, global_translate_std one or three")
         self.rot_noise, self.scale_noise, self.translate_std = [float(v) for v in rot], [float(v) for v in scale], [float(v) for v in std]
+        self.sampling = sampler is not None and not self.identity  # (the reference samples inside its train / augmenting branch only)
         self.rng = np.random.default_rng(seed)
         self._perm_dev = collections.OrderedDict()
 
@@ -201,13 +231,246 @@ class GlobalAugment(object):
             raise ValueError("GlobalAugment: %d clouds, %d rows of parameters, gt_boxes %s" % (len(clouds), params.shape[0], tuple(boxes.shape)))
         recs = self.record(params, device=boxes.device)
         out = dict(batch)
-        out["clouds"] = [hip_ops.augment_points(c, recs[b], torch.empty_like(c), perm=self.permutation(c.shape[0], c.device))
-                         for b, c in enumerate(clouds)]
-        out["gt_boxes"] = hip_ops.augment_boxes(boxes, batch["gt_counts"], recs)
+        if not self.sampling:
+            pasted = [None] * len(clouds)
+            out["gt_boxes"] = hip_ops.augment_boxes(boxes, batch["gt_counts"], recs)
+        else:  # sampling comes first: the transforms see the new rows and the new counts
+            cand, accepted, plan = self._sample(batch, out)
+            pasted = [(cand[b], accepted[b], plan[b]) for b in range(len(clouds))]
+            hip_ops.augment_boxes(out["gt_boxes"], out["gt_counts"], recs, out=out["gt_boxes"])
+        out["clouds"] = [self._cloud(c, recs[b], pasted[b]) for b, c in enumerate(clouds)]
         out["aug_params"] = params
         if self.warp_bev and batch.get("bev_map") is not None:
             out["bev_map"] = self.warp_map(batch["bev_map"], params)
         return out
+
+
+    def _sample(self, batch, out):
+        """GT-database sampling into ``out``: the new ground truth, the candidates and the kernel's reports; returns the per-sample
+        views (cand, accepted, plan) the clouds are pasted from"""
+        s = self.sampler
+        boxes = batch["gt_boxes"]
+        dev = boxes.device
+        cand = batch.get("gt_sample_candidates")
+        if cand is None:
+            cand = s.draw(boxes.shape[0])
+        cand = np.ascontiguousarray(cand, np.int32)
+        if cand.shape != (boxes.shape[0], s.K):
+            raise ValueError("gt_sample_candidates %s: expected [%d, %d]" % (cand.shape, boxes.shape[0], s.K))
+        cand_dev = torch.from_numpy(cand).to(dev)
+        traj = batch.get("gt_trajectory")
+        # on clones: the rows at or past the new counts stay what the batch holds there
+        res = hip_ops.gt_sample_select(boxes.clone(), batch["gt_counts"].clone(), batch["gt_classes"].clone(), s.database, cand_dev, s.records,
+                                       s.rate, s.point_cap, trajectory=traj.clone() if traj is not None else None, out="inplace")
+        out["gt_boxes"], out["gt_counts"], out["gt_classes"] = res["boxes"], res["counts"], res["classes"]
+        if traj is not None:
+            out["gt_trajectory"] = res["trajectory"]
+        out["gt_sample_candidates"], out["gt_sample_status"] = cand, res["status"]
+        out["gt_sample_accepted"], out["gt_sample_points"] = res["accepted"], res["n_points"]
+        return cand_dev, res["accepted"], res["plan"]
+
+    def _cloud(self, c, rec, pasted):
+        """one cloud: [the sampled slots ; the scene], shuffled and transformed"""
+        if pasted is None:
+            return hip_ops.augment_points(c, rec, torch.empty_like(c), perm=self.permutation(c.shape[0], c.device))
+        cand, accepted, plan = pasted
+        cap, n = self.sampler.point_cap, int(c.shape[0])
+        stage = torch.empty((cap + n, c.shape[1]), dtype=torch.float32, device=c.device)
+        hip_ops.gt_sample_points(self.sampler.database, cand, accepted, plan, stage, cap)
+        stage[cap:].copy_(c)
+        return hip_ops.augment_points(stage, rec, torch.empty_like(stage), perm=self.permutation(cap + n, c.device))
+
+
+# ------------------------------------------------------------------------------------------------------------------ GT-database sampling
+_TRAJECTORY = ("static", "linear", "nonlinear")  # the ids targets.py uses
+
+
+def check_db_sampler_cfg(db_cfg):
+    """NotImplementedError for what a ``db_sampler`` dict can ask for that is not built: per-object rotation noise (a non-empty
+    ``global_random_rotation_range_per_object`` whose ends differ by >= 1e-3: noise_per_object_v3_ / rot_transform) and group sampling
+    (a group dict with more than one class)."""
+    rot = _get(db_cfg, "global_random_rotation_range_per_object")
+    if rot is not None:
+        rot = list(rot) if isinstance(rot, (list, tuple, np.ndarray)) else [-rot, rot]
+        if len(rot) > 0 and (len(rot) != 2 or abs(float(rot[0]) - float(rot[1])) >= 1e-3):
+            raise NotImplementedError("db_sampler: global_random_rotation_range_per_object = %r (per-object rotation noise, "
+                                      "noise_per_object_v3_ and rot_transform) is not built; every shipped config has [0, 0]" % (rot,))
+    for g in _get(db_cfg, "sample_groups", []) or []:
+        if len(g) > 1:
+            raise NotImplementedError("db_sampler: group sampling (a sample group with more than one class, %r) is not built" % (dict(g),))
+
+
+class GTDatabase(object):
+    """The ground-truth database on the device, as fd_gt_sample_select / fd_gt_sample_points read it: ``boxes`` [M, Tdb, 12] fp32 (an
+    entry's box at every timestep it has, zeros behind them), ``steps`` [M] int32 (>= 1), ``classes`` [M] int32 (1-based ids over
+    ``class_names``), ``trajectory`` [M] int32 (0 static, 1 linear, 2 nonlinear: targets.py's ids), ``offsets`` [M + 1] int64 and
+    ``points`` [P, ndim] fp32 (object-centred, entry e owns the rows offsets[e]..offsets[e + 1]).  ``host`` keeps numpy copies of the
+    small arrays for the sampler."""
+
+    def __init__(self, boxes, steps, classes, trajectory, points, offsets, device, class_names=None):
+        boxes = np.ascontiguousarray(boxes, np.float32)
+        points = np.ascontiguousarray(points, np.float32)
+        steps, classes, trajectory = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (steps, classes, trajectory))
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        M = boxes.shape[0]
+        if boxes.ndim != 3 or boxes.shape[2] != 12 or M < 1 or boxes.shape[1] < 1:
+            raise ValueError("GTDatabase: boxes must be [M, Tdb, 12] with M, Tdb >= 1, got %s" % (boxes.shape,))
+        if points.ndim != 2 or points.shape[1] not in (4, 5):
+            raise ValueError("GTDatabase: points must be [P, 4] or [P, 5], got %s" % (points.shape,))
+        if len(steps) != M or len(classes) != M or len(trajectory) != M or len(offsets) != M + 1:
+            raise ValueError("GTDatabase: steps, classes and trajectory take %d values, offsets %d" % (M, M + 1))
+        if steps.min() < 1 or steps.max() > boxes.shape[1]:
+            raise ValueError("GTDatabase: steps must lie in [1, Tdb = %d]" % boxes.shape[1])
+        if offsets[0] != 0 or np.any(np.diff(offsets) < 0) or offsets[-1] != points.shape[0]:
+            raise ValueError("GTDatabase: offsets must rise from 0 to the %d rows of points" % points.shape[0])
+        self.class_names = list(class_names) if class_names is not None else None
+        self.host = dict(steps=steps, classes=classes, trajectory=trajectory, offsets=offsets, rows=np.diff(offsets))
+        self.device = torch.device(device)
+        self.boxes, self.points = torch.from_numpy(boxes).to(self.device), torch.from_numpy(points).to(self.device)
+        self.steps, self.classes, self.trajectory = (torch.from_numpy(v).to(self.device) for v in (steps, classes, trajectory))
+        self.offsets = torch.from_numpy(offsets).to(self.device)
+
+    def __len__(self):
+        return int(self.boxes.shape[0])
+
+    @classmethod
+    def from_arrays(cls, boxes, steps, classes, trajectory, points, offsets, device, class_names=None):
+        return cls(boxes, steps, classes, trajectory, points, offsets, device, class_names=class_names)
+
+    @classmethod
+    def from_dbinfos(cls, db_infos, root, class_names, num_point_features, db_prep_steps=(), device="cuda"):
+        """From the reference's database: ``db_infos`` (the dict create_gt_database.py pickles, class name -> list of entries, or the
+        path of that pickle) and the ``.bin`` files its ``path`` entries name below ``root``.  ``db_prep_steps`` as in a config:
+        ``filter_by_min_num_points`` (per class, on ``num_points_in_gt``) and ``filter_by_difficulty``, the latter evaluated as the
+        reference evaluates it -- ``info["difficulty"] not in removed`` with the list-valued difficulty the database writer stores, so
+        the shipped ``[-1]`` removes nothing.  Names and trajectory strings (those of timestep 0) become targets.py's ids; classes
+        outside ``class_names`` are left out.  Entries keep the order of the pickle, class after class."""
+        import os
+        import pickle
+
+        if isinstance(db_infos, (str, bytes, os.PathLike)):
+            with open(db_infos, "rb") as f:
+                db_infos = pickle.load(f)
+        infos = {k: list(v) for k, v in db_infos.items()}
+        for step in db_prep_steps or ():
+            if "filter_by_difficulty" in step:
+                removed = step["filter_by_difficulty"]
+                infos = {k: [i for i in v if i["difficulty"] not in removed] for k, v in infos.items()}
+            elif "filter_by_min_num_points" in step:
+                for name, min_num in dict(step["filter_by_min_num_points"]).items():
+                    if name in infos and min_num > 0:
+                        infos[name] = [i for i in infos[name] if i["num_points_in_gt"] >= min_num]
+            else:
+                raise ValueError("unknown database prep type: %r" % (step,))
+        class_names = list(class_names)
+        first = lambda v: v if isinstance(v, str) else v[0]
+        rows, steps, classes, traj, points = [], [], [], [], []
+        for name, entries in infos.items():
+            if name not in class_names:
+                continue
+            for info in entries:
+                b = np.asarray(info["box3d_lidar"], np.float32).reshape(-1, 12)
+                tr = first(info["trajectory"])
+                if tr not in _TRAJECTORY:
+                    raise KeyError("%s_%s" % (tr, name))
+                p = np.fromfile(os.path.join(str(root), info["path"]), dtype=np.float32).reshape(-1, int(num_point_features))
+                rows.append(b), steps.append(len(b)), classes.append(class_names.index(first(info["name"])) + 1)
+                traj.append(_TRAJECTORY.index(tr)), points.append(p)
+        if not rows:
+            raise ValueError("GTDatabase.from_dbinfos: no entry of the classes %r is left" % (class_names,))
+        boxes = np.zeros((len(rows), max(steps), 12), np.float32)
+        for e, b in enumerate(rows):
+            boxes[e, :len(b)] = b
+        offsets = np.concatenate([[0], np.cumsum([len(p) for p in points])])
+        return cls(boxes, steps, classes, traj, np.concatenate(points), offsets, device, class_names=class_names)
+
+
+class _BatchSampler(object):
+    """The reference's BatchSampler (det3d/core/sampler/preprocess.py:19-54) over n indices: a shuffled list read in slices; a draw
+    that would reach the end (``idx + num >= n``) returns what is left -- possibly fewer than asked for -- and reshuffles."""
+
+    def __init__(self, n, rng):
+        self._indices, self._rng, self._idx, self._n = np.arange(int(n)), rng, 0, int(n)
+        rng.shuffle(self._indices)
+
+    def sample(self, num):
+        if self._idx + num >= self._n:
+            ret = self._indices[self._idx:].copy()
+            self._rng.shuffle(self._indices)
+            self._idx = 0
+        else:
+            ret = self._indices[self._idx:self._idx + num].copy()  # (the reference reads its view at once)
+            self._idx += num
+        return ret
+
+
+class GTSampler(object):
+    """The host half of GT-database sampling: draws, per sample and group, the database entries fd_gt_sample_select chooses from.
+
+    ``sample_groups``: a config's list of one-entry dicts, ``{"car": 2}`` for the standard sampler or ``{"static_car": 2}`` (trajectory
+    type + class) for any other ``sampler_type``; ``rate`` as in the config.  Group g owns ``K_g = max(0, round(rate * max_g))`` slots of
+    the ``K = sum K_g`` (<= 64) columns of ``draw(B)``; ``records`` are the kernel's group records.  Every group pool (the entries of
+    the class, for a typed group those of its trajectory type) has a BatchSampler restatement driven by the object's own
+    ``numpy.random.Generator`` (``seed``); the reference's global ``np.random`` stream is not reproduced.
+
+    Two intended differences from the reference.  (1) The host cannot see the per-class ground-truth counts of a batch that lives on
+    the device, so it always draws K_g entries and the kernel uses the first ``round(rate * (max_g - count_g))`` of them: the pools
+    are consumed faster.  (A typed group also draws from a pool of its own type instead of skipping through the class's pool.)
+    (2) The reference mutates a database entry on its first use (``sample["box3d_lidar"] = sample["box3d_lidar"][0]``), so a second
+    draw of the same entry has lost its forecasts; here every draw sees all timesteps.
+
+    ``point_cap`` (None: the bound that can never overflow, the sum over groups of K_g x the largest entry of the pool): the rows every
+    cloud grows by -- the accepted entries' points and sentinel rows behind them."""
+
+    def __init__(self, database, sample_groups, rate=1.0, sampler_type="standard", seed=None, point_cap=None):
+        if database.class_names is None:
+            raise ValueError("GTSampler: the database needs class_names to resolve the groups")
+        self.database, self.rate, self.sampler_type = database, float(rate), sampler_type
+        self.rng = np.random.default_rng(seed)
+        host = database.host
+        self.records, self._pools, self._entries = [], [], []
+        pools, first, bound = {}, 0, 0
+        for g in sample_groups:
+            if len(g) != 1:
+                raise NotImplementedError("GTSampler: group sampling (a sample group with more than one class, %r) is not built" % (dict(g),))
+            (key, max_num), = dict(g).items()
+            tr = -1
+            name = key
+            if sampler_type != "standard":
+                trs, name = key.split("_")
+                if trs not in _TRAJECTORY:
+                    raise KeyError(key)
+                tr = _TRAJECTORY.index(trs)
+            if name not in database.class_names:
+                raise ValueError("GTSampler: group %r names a class outside class_names %r" % (key, database.class_names))
+            cid = database.class_names.index(name) + 1
+            k = max(0, int(np.round(self.rate * max_num)))
+            if (cid, tr) not in pools:
+                entries = np.nonzero((host["classes"] == cid) & ((host["trajectory"] == tr) | (tr < 0)))[0].astype(np.int32)
+                pools[(cid, tr)] = (entries, _BatchSampler(len(entries), self.rng) if len(entries) else None)
+            entries, pool = pools[(cid, tr)]
+            self._entries.append(entries), self._pools.append(pool)
+            self.records.append((cid, tr, int(max_num), first, k))
+            first += k
+            bound += k * (int(host["rows"][entries].max()) if len(entries) else 0)
+        self.K = first
+        if not 1 <= self.K <= hip_ops.GT_SAMPLE_MAX_K or len(self.records) > hip_ops.GT_SAMPLE_MAX_GROUPS:
+            raise ValueError("GTSampler: %d slots in %d groups; the kernel takes 1..%d slots in at most %d groups"
+                             % (self.K, len(self.records), hip_ops.GT_SAMPLE_MAX_K, hip_ops.GT_SAMPLE_MAX_GROUPS))
+        self.point_cap = int(bound if point_cap is None else point_cap)
+        if self.point_cap < 0:
+            raise ValueError("GTSampler: point_cap = %d" % self.point_cap)
+
+    def draw(self, B):
+        """int32 [B, K]: per sample, group after group, the drawn entries; -1 where a pool is empty or its draw came up short"""
+        cand = np.full((int(B), self.K), -1, np.int32)
+        for b in range(int(B)):
+            for (_, _, _, first, k), entries, pool in zip(self.records, self._entries, self._pools):
+                if pool is None or k == 0:
+                    continue
+                idx = pool.sample(k)
+                cand[b, first:first + len(idx)] = entries[idx]
+        return cand
 
 
 def _invert_affine(m):
@@ -267,5 +530,5 @@ def identity_params(B):
     return out
 
 
-__all__ = ["GlobalAugment", "reference_permutation", "identity_params", "filter_gt_outside_range", "bev_range", "check_bev_size",
+__all__ = ["GlobalAugment", "GTDatabase", "GTSampler", "check_db_sampler_cfg", "reference_permutation", "identity_params", "filter_gt_outside_range", "bev_range", "check_bev_size",
            "RECORD_DTYPE", "MASK_RECORD_DTYPE", "PARAM_FIELDS", "BEV_SIZE"]

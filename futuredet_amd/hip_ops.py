@@ -1913,6 +1913,129 @@ def augment_mask(src, recs, out=None):
     return out
 
 
+# ---- training: GT-database sampling (fd_gt_sample.hip) ----------------------------------------------------------------------------
+GT_SAMPLE_MAX_K, GT_SAMPLE_MAX_GROUPS = 64, 16                 # FD_GT_SAMPLE_MAX_K / _MAX_GROUPS
+GT_SAMPLE_NO_ROW, GT_SAMPLE_NO_POINTS, GT_SAMPLE_COUNTS_DIFFER, GT_SAMPLE_BAD_INDEX = 1, 2, 4, 8  # the bits of status
+GT_SAMPLE_SENTINEL = 1e30                                      # FD_GT_SAMPLE_SENTINEL
+GT_SAMPLE_PLAN_WORDS = 4                                       # struct fd_gt_sample_plan as int32 words: src_row (2), rows, dst_row
+
+
+def _gt_database(db, what):
+    """the five device arrays of a database (augment.GTDatabase or anything with these attributes), checked against one another"""
+    boxes = _dev(db.boxes, "db.boxes", torch.float32)
+    if boxes.dim() != 3 or boxes.shape[2] != 12 or boxes.shape[0] < 1 or boxes.shape[1] < 1:
+        raise FutureDetHipError("%s: db.boxes must be [M, Tdb, 12] with M, Tdb >= 1 (got %s)" % (what, tuple(boxes.shape)))
+    M = int(boxes.shape[0])
+    steps, classes, traj = (_dev(getattr(db, k), "db." + k, torch.int32) for k in ("steps", "classes", "trajectory"))
+    offsets = _dev(db.offsets, "db.offsets", torch.int64)
+    points = _dev(db.points, "db.points", torch.float32)
+    if points.dim() != 2 or points.shape[1] not in (4, 5):
+        raise FutureDetHipError("%s: db.points must be [P, 4] or [P, 5] (got %s)" % (what, tuple(points.shape)))
+    for t, n, name in ((steps, M, "steps"), (classes, M, "classes"), (traj, M, "trajectory"), (offsets, M + 1, "offsets")):
+        if tuple(t.shape) != (n,) or t.device != boxes.device:
+            raise FutureDetHipError("%s: db.%s must be [%d] on %s (got %s on %s)" % (what, name, n, boxes.device, tuple(t.shape), t.device))
+    if points.device != boxes.device:
+        raise FutureDetHipError("%s: db.points lives on %s, db.boxes on %s" % (what, points.device, boxes.device))
+    return boxes, steps, classes, traj, offsets, points
+
+
+def gt_sample_groups(groups):
+    """a ctypes array of struct fd_gt_sample_group from rows (class_id, trajectory | -1, max_num, first, n)"""
+    rows = [tuple(int(v) for v in g) for g in groups]
+    if not 1 <= len(rows) <= GT_SAMPLE_MAX_GROUPS or any(len(r) != 5 for r in rows):
+        raise FutureDetHipError("gt_sample_select: 1 to %d group records of (class_id, trajectory, max_num, first, n), got %r"
+                                % (GT_SAMPLE_MAX_GROUPS, rows))
+    return (_lib.GtSampleGroup * len(rows))(*[_lib.GtSampleGroup(*r) for r in rows])
+
+
+def gt_sample_select(boxes, counts, classes, db, cand, groups, rate, point_cap, trajectory=None, out=None, accepted=None, plan=None,
+                     n_points=None, status=None):
+    """fd_gt_sample_select: decides, per sample, which of the drawn database entries ``cand`` [B, K] (int32, -1 = empty) are pasted, and
+    appends their rows to the padded ground truth boxes [B, T, n_max, 12] / counts [B, T] / classes / ``trajectory`` (or None)
+    [B, T, n_max].  ``db``: the device database (augment.GTDatabase); ``groups``: rows (class_id, trajectory | -1, max_num, first, n) or
+    gt_sample_groups' array.  ``out``: None = new tensors (rows at or past the new counts are uninitialised), "inplace" = the inputs
+    themselves, or a tuple (boxes, counts, classes, trajectory | None) that overlaps no input.  Returns a dict: boxes, counts, classes,
+    trajectory, accepted [B, K] int32, plan [B, K, 4] int32 (src_row as two words, rows, dst_row), n_points [B], status [B] (the
+    GT_SAMPLE_* bits).  One launch, no synchronisation."""
+    boxes = _dev(boxes, "boxes", torch.float32)
+    if boxes.dim() != 4 or boxes.shape[3] != 12 or min(boxes.shape[:3]) < 1:
+        raise FutureDetHipError("gt_sample_select: boxes must be [B, T, n_max, 12] with B, T, n_max >= 1 (got %s)" % (tuple(boxes.shape),))
+    B, T, n_max = (int(v) for v in boxes.shape[:3])
+    dev = boxes.device
+    ins = [boxes, _dev(counts, "counts", torch.int32), _dev(classes, "classes", torch.int32),
+           _dev(trajectory, "trajectory", torch.int32) if trajectory is not None else None]
+    names = ["boxes", "counts", "classes", "trajectory"]
+    for t, shape, name in zip(ins, [tuple(boxes.shape), (B, T), (B, T, n_max), (B, T, n_max)], names):
+        if t is not None and (tuple(t.shape) != shape or t.device != dev):
+            raise FutureDetHipError("gt_sample_select: %s must be %s on %s (got %s on %s)" % (name, list(shape), dev, tuple(t.shape), t.device))
+    dbb, dbs, dbc, dbt, dbo, dbp = _gt_database(db, "gt_sample_select")
+    if dbb.device != dev:
+        raise FutureDetHipError("gt_sample_select: the database lives on %s, the batch on %s" % (dbb.device, dev))
+    cand = _dev(cand, "cand", torch.int32)
+    if cand.dim() != 2 or cand.shape[0] != B or not 1 <= cand.shape[1] <= GT_SAMPLE_MAX_K or cand.device != dev:
+        raise FutureDetHipError("gt_sample_select: cand must be int32 [%d, K] with 1 <= K <= %d on %s (got %s)" % (B, GT_SAMPLE_MAX_K, dev, tuple(cand.shape)))
+    K = int(cand.shape[1])
+    if not isinstance(groups, ctypes.Array):
+        groups = gt_sample_groups(groups)
+    if isinstance(out, str):
+        if out != "inplace":
+            raise FutureDetHipError("gt_sample_select: out must be None, \"inplace\" or a tuple of four tensors")
+        outs = list(ins)
+    elif out is None:
+        outs = [torch.empty_like(t) if t is not None else None for t in ins]
+    else:
+        outs = list(out)
+        if len(outs) != 4:
+            raise FutureDetHipError("gt_sample_select: out takes (boxes, counts, classes, trajectory | None)")
+        for i, (t, src, name) in enumerate(zip(outs, ins, names)):
+            if src is None:
+                outs[i] = None
+                continue
+            t = _dev(t, name + "_out", src.dtype)
+            if tuple(t.shape) != tuple(src.shape) or t.device != dev:
+                raise FutureDetHipError("gt_sample_select: %s_out %s does not match %s %s" % (name, tuple(t.shape), name, tuple(src.shape)))
+
+    def small(t, shape, name):
+        if t is None:
+            return torch.empty(shape, dtype=torch.int32, device=dev)
+        t = _dev(t, name, torch.int32)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise FutureDetHipError("gt_sample_select: %s must be int32 %s on %s (got %s)" % (name, list(shape), dev, tuple(t.shape)))
+        return t
+
+    accepted, plan = small(accepted, (B, K), "accepted"), small(plan, (B, K, GT_SAMPLE_PLAN_WORDS), "plan")
+    n_points, status = small(n_points, (B,), "n_points"), small(status, (B,), "status")
+    check(_lib.load().fd_gt_sample_select(_p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), _p(dbb), _p(dbs), _p(dbc), _p(dbt), _p(dbo),
+                                          int(dbb.shape[0]), int(dbb.shape[1]), int(dbp.shape[0]), _p(cand), groups, len(groups), float(rate),
+                                          int(point_cap), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(accepted), _p(plan),
+                                          _p(n_points), _p(status), B, T, n_max, K, _stream()), "fd_gt_sample_select")
+    return dict(boxes=outs[0], counts=outs[1], classes=outs[2], trajectory=outs[3], accepted=accepted, plan=plan, n_points=n_points,
+                status=status)
+
+
+def gt_sample_points(db, cand, accepted, plan, dst, point_cap):
+    """fd_gt_sample_points for ONE sample: cand / accepted int32 [K] and plan int32 [K, 4], the sample's rows of gt_sample_select's
+    arrays.  Fills the rows [0, point_cap) of dst [>= point_cap, ndim] (ndim = the database's) with the accepted entries' points, moved
+    to their boxes' centres, and sentinel rows (1e30, 1e30, 1e30, 0[, 0]) behind them; later rows are not written.  One launch, no
+    synchronisation.  Returns dst."""
+    dbb, _, _, _, _, dbp = _gt_database(db, "gt_sample_points")
+    dst = _dev(dst, "dst", torch.float32)
+    point_cap = int(point_cap)
+    if dst.dim() != 2 or dst.shape[1] != dbp.shape[1] or not 0 <= point_cap <= dst.shape[0] or dst.device != dbp.device:
+        raise FutureDetHipError("gt_sample_points: dst must be [>= point_cap = %d, %d] on %s (got %s on %s)"
+                                % (point_cap, dbp.shape[1], dbp.device, tuple(dst.shape), dst.device))
+    cand, accepted, plan = _dev(cand, "cand", torch.int32), _dev(accepted, "accepted", torch.int32), _dev(plan, "plan", torch.int32)
+    K = int(cand.numel())
+    if cand.dim() != 1 or not 1 <= K <= GT_SAMPLE_MAX_K or tuple(accepted.shape) != (K,) or tuple(plan.shape) != (K, GT_SAMPLE_PLAN_WORDS):
+        raise FutureDetHipError("gt_sample_points: cand and accepted must be int32 [K], plan int32 [K, %d], 1 <= K <= %d (got %s, %s, %s)"
+                                % (GT_SAMPLE_PLAN_WORDS, GT_SAMPLE_MAX_K, tuple(cand.shape), tuple(accepted.shape), tuple(plan.shape)))
+    if cand.device != dst.device or accepted.device != dst.device or plan.device != dst.device:
+        raise FutureDetHipError("gt_sample_points: cand, accepted and plan must live on %s" % (dst.device,))
+    check(_lib.load().fd_gt_sample_points(_p(dbp), int(dbp.shape[0]), int(dbp.shape[1]), _p(dbb), int(dbb.shape[0]), int(dbb.shape[1]), _p(cand),
+                                          _p(accepted), _p(plan), K, _p(dst), point_cap, _stream()), "fd_gt_sample_points")
+    return dst
+
+
 # ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------
 LOSS_MAPS = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")  # fd_loss_task.maps / d_maps, in this order
 

@@ -87,6 +87,11 @@ class AugmentRecord(ctypes.Structure):  # struct fd_augment_record
                 ("tx", ctypes.c_double), ("ty", ctypes.c_double), ("tz", ctypes.c_double)]
 
 
+class GtSampleGroup(ctypes.Structure):  # struct fd_gt_sample_group
+    _fields_ = [("class_id", ctypes.c_int32), ("trajectory", ctypes.c_int32), ("max_num", ctypes.c_int32), ("first", ctypes.c_int32),
+                ("n", ctypes.c_int32)]
+
+
 class AugmentMaskRecord(ctypes.Structure):  # struct fd_augment_mask_record
     _fields_ = [("flip_a", ctypes.c_int32), ("flip_b", ctypes.c_int32), ("m1", ctypes.c_double * 6), ("m2", ctypes.c_double * 6)]
 
@@ -251,6 +256,10 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fd_augment_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fd_augment_mask_check": (c_int, [c_void_p, c_int, c_int, c_int]),
+    "fd_gt_sample_select": (c_int, [c_void_p] * 9 + [c_int, c_int, c_i64, c_void_p, c_void_p, c_int, ctypes.c_double, c_int] + [c_void_p] * 8
+                            + [c_int, c_int, c_int, c_int, c_void_p]),
+    "fd_gt_sample_points": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                    c_void_p]),
     "fd_loss_chunk": (c_int, []),
     "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),

@@ -398,6 +398,22 @@ class _StaticTrainBase(object):
 
             self.gt_range = bev_range(voxel_cfg["range"])
             self.gt_filter_status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        # augment.sampler (an augment.GTSampler): GT-database sampling while the batch is loaded -- the candidates' device copy, the
+        # kernel's reports, and the stage a cloud is assembled in ([the sampled slots ; the scene]) before fd_augment_points reads it
+        self.gt_sample = None
+        if getattr(augment, "sampling", False):
+            s = augment.sampler
+            if s.database.points.shape[1] != self.ndim or s.database.points.device != dev:
+                raise ValueError("%s: the sampler's database holds %d-column points on %s, the step takes %d columns on %s"
+                                 % (name, s.database.points.shape[1], s.database.points.device, self.ndim, dev))
+            if s.point_cap >= self.capacity:
+                raise ValueError("%s: point_cap = %d leaves no room for a scene in clouds of capacity %d" % (name, s.point_cap, self.capacity))
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.gt_sample = dict(cand=torch.full((B, s.K), -1, **i32), accepted=torch.zeros((B, s.K), **i32),
+                                  plan=torch.zeros((B, s.K, hip_ops.GT_SAMPLE_PLAN_WORDS), **i32), n_points=torch.zeros((B,), **i32),
+                                  status=torch.zeros((B,), **i32), groups=hip_ops.gt_sample_groups(s.records),
+                                  stage=torch.zeros((B, s.point_cap + self.capacity, self.ndim), dtype=torch.float32, device=dev))
+        self.last_gt_sample_candidates = None
         self._ring, self._slot = None, 0
         self.iteration = 0
         self.outputs, self.level_counts = None, None
@@ -411,13 +427,15 @@ class _StaticTrainBase(object):
     # -- inputs
     def _pinned(self):
         """a slot of the ring of pinned staging buffers (cloud counts, the six scalars, the event of its last copy, the augmentation
-        records, the mask records), free again once its last copy has run"""
+        records, the mask records, the GT-sampling candidates), free again once its last copy has run"""
         if self._ring is None:
             self._ring = [[torch.empty((self.B,), dtype=torch.int32).pin_memory(), torch.empty((6,), dtype=torch.float64).pin_memory(), None,
                            torch.empty((self.B, hip_ops.AUGMENT_RECORD_DOUBLES), dtype=torch.float64).pin_memory()
                            if self.augment is not None else None,
                            torch.empty((self.B, hip_ops.AUGMENT_MASK_RECORD_DOUBLES), dtype=torch.float64).pin_memory()
-                           if getattr(self, "mask_rec", None) is not None else None]
+                           if getattr(self, "mask_rec", None) is not None else None,
+                           torch.empty(tuple(self.gt_sample["cand"].shape), dtype=torch.int32).pin_memory()
+                           if getattr(self, "gt_sample", None) is not None else None]
                           for _ in range(8)]
         slot = self._ring[self._slot % len(self._ring)]
         self._slot += 1
@@ -441,12 +459,31 @@ class _StaticTrainBase(object):
             raise ValueError("aug_params %s: expected [%d, %d] (%s)" % (params.shape, self.B, len(PARAM_FIELDS), ", ".join(PARAM_FIELDS)))
         return params
 
+    def _gt_candidates(self, batch):
+        """this batch's GT-sampling candidates [B, K]: batch["gt_sample_candidates"], else a draw"""
+        s = self.augment.sampler
+        cand = batch.get("gt_sample_candidates")
+        if cand is None:
+            cand = s.draw(self.B)
+        cand = np.asarray(cand, np.int32)
+        if cand.shape != (self.B, s.K):
+            raise ValueError("gt_sample_candidates %s: expected [%d, %d]" % (cand.shape, self.B, s.K))
+        return cand
+
     def _load(self, batch, iteration):
         clouds = batch["clouds"]
         if len(clouds) != self.B:
             raise ValueError("the step was built for batches of %d clouds, got %d" % (self.B, len(clouds)))
         aug = self.augment
+        gs = getattr(self, "gt_sample", None)
+        grow = aug.sampler.point_cap if gs is not None else 0  # every cloud grows by exactly this many rows
+        if gs is not None:
+            for c in clouds:  # refused before anything of the step changes
+                if int(c.shape[0]) + grow > self.capacity:
+                    raise ValueError("cloud of %d rows + point_cap = %d sampled rows does not fit the step's capacity of %d rows"
+                                     % (int(c.shape[0]), grow, self.capacity))
         params = self._aug_params(batch) if aug is not None else None  # (drawn or refused before anything of the step changes)
+        cand = self._gt_candidates(batch) if gs is not None else None
         warp = getattr(self, "mask_rec", None) is not None
         mask_recs = aug.mask_record(params) if warp else None
         if self.bev is not None:
@@ -468,23 +505,59 @@ class _StaticTrainBase(object):
             if warp:
                 slot[4].numpy()[:] = mask_recs.view(np.float64).reshape(self.B, -1)
                 self.mask_rec.copy_(slot[4], non_blocking=True)
+        if gs is not None:  # the ground truth first: the clouds are pasted from what the selection accepts
+            slot[5].numpy()[:] = cand
+            gs["cand"].copy_(slot[5], non_blocking=True)
+            self.last_gt_sample_candidates = cand
+            self._load_gt(batch)
         for b, c in enumerate(clouds):
             n = int(c.shape[0])
             if n > self.capacity or c.shape[1] != self.ndim:
                 raise ValueError("cloud of %d x %d rows does not fit the step's %d x %d buffer" % (n, c.shape[1], self.capacity, self.ndim))
             if aug is None:
                 self.points[b, :n].copy_(c, non_blocking=True)
-            else:  # the shuffle and the transforms, straight from the batch's tensor
+            elif gs is None:  # the shuffle and the transforms, straight from the batch's tensor
                 hip_ops.augment_points(c, self.aug_rec[b], self.points[b], perm=aug.permutation(n, self.device), n_rows=n)
-            counts_host[b] = n
+            else:  # [the sampled slots ; the scene] in the stage, then one shuffle-and-transform over all of it
+                stage = gs["stage"][b]
+                hip_ops.gt_sample_points(aug.sampler.database, gs["cand"][b], gs["accepted"][b], gs["plan"][b], stage, grow)
+                stage[grow:grow + n].copy_(c, non_blocking=True)
+                hip_ops.augment_points(stage, self.aug_rec[b], self.points[b], perm=aug.permutation(n + grow, self.device), n_rows=n + grow)
+            counts_host[b] = n + grow
         self.counts.copy_(counts_host, non_blocking=True)
         self.hyper.copy_(hyper_host, non_blocking=True)
         slot[2] = torch.cuda.Event()
         slot[2].record()
+        if gs is None:
+            self._load_gt(batch)
+        if self.bev is not None:
+            if warp:  # the batch's map is the unwarped one
+                hip_ops.augment_mask(batch["bev_map"].contiguous(), self.mask_rec, out=self.bev)
+            else:
+                self.bev.copy_(batch["bev_map"], non_blocking=True)
+
+    def _load_gt(self, batch):
+        """the padded ground truth into the static buffers: copy, (GT-database sampling,) augmentation, (range filter)"""
+        aug, gs = self.augment, getattr(self, "gt_sample", None)
         boxes, gcounts, classes = batch["gt_boxes"], batch["gt_counts"], batch["gt_classes"]
         n = int(boxes.shape[2])
         if tuple(boxes.shape[:2]) != (self.B, self.T) or n > self.max_gt or boxes.shape[3] != 12:
             raise ValueError("gt_boxes %s do not fit the step's [%d, %d, <= %d, 12] buffer" % (tuple(boxes.shape), self.B, self.T, self.max_gt))
+        if gs is not None:  # copy -> select in place (the step's counts from here on) -> transform -> filter
+            self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
+            self.gt_counts.copy_(gcounts, non_blocking=True)
+            self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
+            if self.gt_trajectory is not None:
+                self.gt_trajectory[:, :, :n].copy_(batch["gt_trajectory"], non_blocking=True)
+            s = aug.sampler
+            hip_ops.gt_sample_select(self.gt_boxes, self.gt_counts, self.gt_classes, s.database, gs["cand"], gs["groups"], s.rate, s.point_cap,
+                                     trajectory=self.gt_trajectory, out="inplace", accepted=gs["accepted"], plan=gs["plan"],
+                                     n_points=gs["n_points"], status=gs["status"])
+            hip_ops.augment_boxes(self.gt_boxes, self.gt_counts, self.aug_rec, out=self.gt_boxes)
+            if getattr(self, "filter_gt", False):
+                hip_ops.gt_range_filter(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_range, trajectory=self.gt_trajectory,
+                                        out="inplace", status=self.gt_filter_status)
+            return
         if aug is not None and n == self.max_gt and boxes.is_contiguous():
             hip_ops.augment_boxes(boxes, gcounts, self.aug_rec, out=self.gt_boxes)
         else:
@@ -500,11 +573,6 @@ class _StaticTrainBase(object):
         if filter_gt:  # in place on the static rows; the kernel reads the batch's counts and writes the step's
             hip_ops.gt_range_filter(self.gt_boxes, gcounts.contiguous(), self.gt_classes, self.gt_range, trajectory=self.gt_trajectory,
                                     out=(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_trajectory), status=self.gt_filter_status)
-        if self.bev is not None:
-            if warp:  # the batch's map is the unwarped one
-                hip_ops.augment_mask(batch["bev_map"].contiguous(), self.mask_rec, out=self.bev)
-            else:
-                self.bev.copy_(batch["bev_map"], non_blocking=True)
 
     # -- the step
     def _body(self, static):
@@ -606,6 +674,14 @@ class StaticTrainStep(_StaticTrainBase):
     timestep, the objects whose timestep-0 box has no BEV corner inside the x / y bounds of ``voxel_cfg["range"]`` -- the train-mode
     filter of the reference's Voxelization stage -- in place on the static ground truth; ``gt_counts`` is then written by the kernel
     and ``gt_filter_status`` [B] counts the timesteps of a sample whose count differed from timestep 0's.  Works with ``augment=None``.
+
+    GT-database sampling (``augment=GlobalAugment(..., sampler=GTSampler(...))``; without a sampler today's launches and buffers): the
+    step draws the candidates (or takes ``batch["gt_sample_candidates"]`` [B, K]; the last ones are ``last_gt_sample_candidates``),
+    uploads them through the same ring, copies the ground truth into the static buffers, runs fd_gt_sample_select in place on them,
+    then fd_augment_boxes and the range filter with the step's counts; every cloud is assembled as [the sampled slots ; the scene] in
+    a stage of [B, point_cap + capacity, ndim] (fd_gt_sample_points, a copy) and goes through one fd_augment_points over
+    n + point_cap rows, so the cloud counts stay host-known.  A cloud with n + point_cap > capacity raises ValueError before anything
+    of the step changes.  ``gt_sample["accepted"]`` [B, K], ``["n_points"]`` and ``["status"]`` [B] hold the kernel's reports.
 
     ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
     device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward

@@ -926,6 +926,86 @@ int fd_augment_mask(const float *src, const fd_augment_mask_record *recs, float 
 int fd_augment_mask_check(const fd_augment_mask_record *recs_host, int B, int H, int W);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Training: ground-truth database sampling, "GT-AUG" (fd_gt_sample.hip) -- what Preprocess does with its db_sampler before the global
+ * transforms (det3d/datasets/pipelines/preprocess.py:147-182; DataBaseSamplerV2.sample_all / sample_class_v2,
+ * det3d/core/sampler/sample_ops.py:101-253, 275-351; box_collision_test, det3d/core/sampler/preprocess.py:881-964).  The host draws the
+ * database entries (augment.GTSampler); which of them are pasted is decided here, per sample, from the sample's own ground truth.
+ * Purely additive: fd_abi_version() stays 8.  Graph-capturable, no atomics, no allocation, no workspace, no synchronisation.
+ *
+ * The database, in device memory: db_boxes [M, Tdb, 12] fp32 (16-byte aligned; an entry's box rows, timestep 0 first), db_steps [M]
+ *   (valid timesteps of an entry, >= 1), db_class [M], db_traj [M] int32, db_point_offset [M + 1] int64 (entry e owns the rows
+ *   [offset[e], offset[e + 1]) of db_points [P, ndim] fp32, object-centred).
+ *
+ * fd_gt_sample_select: one launch for the batch, one workgroup per sample.  boxes [B, T, n_max, 12] fp32, counts [B, T], classes and
+ *   trajectory (or NULL) [B, T, n_max] int32 as for fd_gt_range_filter; cand [B, K] int32 holds the drawn entries, -1 = an empty slot;
+ *   groups_host [G] in HOST memory (copied into the launch): group g owns the slots [first, first + n), the groups follow one another in
+ *   slot order.  Per sample, with c_t = clamp(counts[b, t], 0, n_max):
+ *   1. count_g = the objects i < c_0 of timestep 0 with classes == class_id and (trajectory < 0 or trajectory[b, 0, i] == trajectory);
+ *      num_g = max(0, rint(rate * double(max_num - count_g))), round half to even (np.round).  The first num_g slots of the group that
+ *      hold an entry TAKE PART.  A slot holds an entry when its index e lies in [0, M) and offset[e] <= offset[e + 1] <= P; any other
+ *      value but -1 makes it an empty slot and sets FD_GT_SAMPLE_BAD_INDEX.
+ *   2. BEV corners, in the form fd_gt_range_filter's text defines (every operation one fp32 operation): s = fl32(sin(double(a))),
+ *      c = fl32(cos(double(a))); corner k has the offsets (-w/2, -l/2), (-w/2, +l/2), (+w/2, +l/2), (+w/2, -l/2);
+ *      x_k = (ox c + oy s) + x, y_k = (-(ox s) + oy c) + y.  The angle a is column 11 for a slot among the slots of its own group (a
+ *      CANDIDATE) and column 10 for a ground-truth row and for an accepted slot of an earlier group (an OBSTACLE): the reference reads
+ *      gt_boxes[:, -2] for the one and [:, -1] for the other.  A stand-up box is the min / max of the four corners.
+ *   3. collide(p, q) = box_collision_test(boxes = p, qboxes = q) for one pair, p always the candidate whose row is being judged:
+ *      iw = min(p.xmax, q.xmax) - max(p.xmin, q.xmin) must be > 0, then ih likewise; then, for the edges AB of p (k = 0..3, B = corner
+ *      k + 1 mod 4) and CD of q (l = 0..3): acd = (Dy - Ay)(Cx - Ax) > (Cy - Ay)(Dx - Ax), bcd likewise with B, and when they differ
+ *      abc = (Cy - Ay)(Bx - Ax) > (By - Ay)(Cx - Ax), abd = (Dy - Ay)(Bx - Ax) > (By - Ay)(Dx - Ax); abc != abd is a collision.
+ *      Otherwise containment: q lies inside p when for all corners Q of q and all k, with V = -(P_k - P_(k + 1 mod 4)),
+ *      cross = V.y (P_k.x - Q.x), cross = cross - V.x (P_k.y - Q.y) is NOT >= 0; then p inside q the same way.  Either is a collision.
+ *      (This is the function as numba compiles it; see DESIGN.md on `ret[i, j] is False`.)  A slot never collides with itself.
+ *   4. The walk: group after group, slot after slot among those that take part.  The obstacles of a slot are the ground-truth rows
+ *      i < c_0 of timestep 0, the ACCEPTED slots of earlier groups, and the slots of its own group that take part and have not been
+ *      rejected (accepted ones and those still to come).  A slot that collides with an obstacle is rejected.  So is one that would
+ *      not fit: max_t c_t + (accepted so far) >= n_max sets FD_GT_SAMPLE_NO_ROW, rows(e) > point_cap - (points accepted so far) sets
+ *      FD_GT_SAMPLE_NO_POINTS (tested in this order, after the collision).  Every other slot is accepted.
+ *   5. The r-th accepted slot (slot order), entry e, becomes row c_t + r of every timestep t: columns 0..5 of db_boxes[e, 0], columns
+ *      6..11 of db_boxes[e, t < min(db_steps[e], Tdb) ? t : 0], classes = db_class[e], trajectory = db_traj[e]; counts_out[b, t] =
+ *      c_t + accepted.  A sample with counts[b, t] != counts[b, 0] for some t sets FD_GT_SAMPLE_COUNTS_DIFFER.  Rows at or past the new
+ *      counts are not written.  Either every output is its input (in place) or none overlaps an input; out of place the rows below c_t
+ *      are copied.
+ *   6. accepted [B, K] = 0 / 1; plan [B, K] (16-byte aligned): src_row = offset[e], rows = rows(e) for an accepted slot and 0, 0 for
+ *      any other, dst_row = the rows of the accepted slots before it; n_points [B] = their total (<= point_cap); status [B] = the bits.
+ *   FD_EINVAL for: B < 1, T outside [1, FD_GT_SAMPLE_MAX_T], n_max outside [1, FD_RANGE_FILTER_MAX_N], K outside [1, FD_GT_SAMPLE_MAX_K],
+ *   G outside [1, FD_GT_SAMPLE_MAX_GROUPS], M or Tdb < 1, P < 0, point_cap outside [0, FD_AUGMENT_MAX_ROWS], a rate that is negative or
+ *   not finite, group records that overlap, are out of slot order or run past K, a group with trajectory >= 0 while trajectory is
+ *   NULL, null or misaligned pointers, partially overlapping or mixed in-place / out-of-place outputs.
+ *
+ * fd_gt_sample_points: one launch per cloud.  cand, accepted, plan: the sample's rows [K] of the arrays above.  Fills the rows
+ *   [0, point_cap) of dst [>= point_cap, ndim], ndim 4 or 5: row dst_row + k of an accepted slot = db_points[src_row + k] with
+ *   fl32(x + cx), fl32(y + cy), fl32(z + cz), (cx, cy, cz) = columns 0..2 of db_boxes[e, 0], the other columns bit for bit; every
+ *   other row is the SENTINEL (FD_GT_SAMPLE_SENTINEL x 3, 0[, 0]): a point no voxeliser keeps under any shipped transform.  Rows at or
+ *   past point_cap are not written.  A plan entry that does not lie inside db_points writes sentinels; nothing is read out of bounds.
+ *   ndim 4 with 16-byte aligned db_points and dst moves a row as one 16-byte access; otherwise scalar accesses.
+ *   FD_EINVAL for: ndim not 4 or 5, K out of range, M or Tdb < 1, P < 0, point_cap outside [0, FD_AUGMENT_MAX_ROWS], null or misaligned
+ *   pointers (plan 8 bytes, the others 4), dst overlapping db_points.  point_cap = 0 is a no-op.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_GT_SAMPLE_MAX_K 64
+#define FD_GT_SAMPLE_MAX_GROUPS 16
+#define FD_GT_SAMPLE_MAX_T 64
+#define FD_GT_SAMPLE_SENTINEL 1e30f
+#define FD_GT_SAMPLE_NO_ROW 1
+#define FD_GT_SAMPLE_NO_POINTS 2
+#define FD_GT_SAMPLE_COUNTS_DIFFER 4
+#define FD_GT_SAMPLE_BAD_INDEX 8
+typedef struct fd_gt_sample_group {
+    int32_t class_id, trajectory /* -1: any */, max_num, first, n;
+} fd_gt_sample_group;
+typedef struct fd_gt_sample_plan {
+    int64_t src_row;
+    int32_t rows, dst_row;
+} fd_gt_sample_plan;
+int fd_gt_sample_select(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory, const float *db_boxes,
+                        const int32_t *db_steps, const int32_t *db_class, const int32_t *db_traj, const int64_t *db_point_offset, int M, int Tdb,
+                        int64_t P, const int32_t *cand, const fd_gt_sample_group *groups_host, int G, double rate, int point_cap,
+                        float *boxes_out, int32_t *counts_out, int32_t *classes_out, int32_t *trajectory_out, int32_t *accepted,
+                        fd_gt_sample_plan *plan, int32_t *n_points, int32_t *status, int B, int T, int n_max, int K, fd_stream_t stream);
+int fd_gt_sample_points(const float *db_points, int64_t P, int ndim, const float *db_boxes, int M, int Tdb, const int32_t *cand,
+                        const int32_t *accepted, const fd_gt_sample_plan *plan, int K, float *dst, int point_cap, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
  * det3d/models/losses/centernet_loss.py as center_head.py:396-539 combines them, forward terms and the gradient of every head map.
  * Purely additive: fd_abi_version() stays 8.  fp32 maps, contiguous [B, channels, H, W].
