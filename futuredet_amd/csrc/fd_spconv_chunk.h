@@ -79,6 +79,7 @@ struct Layout {
     int bytes;
 };
 constexpr int acc_copy_floats(int tm, int cout) { return (tm + 1) * cout; }  // TM rows + the scratch row
+constexpr int acc_span(int cout) { return cout >= 64 ? 256 : cout * 4; }     // bytes within which the slot swizzle permutes (acc_swizzle)
 constexpr Layout layout(int tm, int cout, int ts, int item) {
     Layout l{};
     l.list = 0;
@@ -88,6 +89,8 @@ constexpr Layout layout(int tm, int cout, int ts, int item) {
     l.cnt = l.items + (int)sizeof(unsigned short) * 4 * l.item_slot;
     l.pad = l.cnt + 112;  // kMaxTaps * 4 counts, rounded up to 16 bytes
     l.acc = l.pad + (int)sizeof(int) * item;
+    // the 32-pair kernel addresses its slots in XOR-linear form (acc_row_term): its tile copies start at multiples of the swizzle's span
+    if (item == 32) l.acc = (l.acc + acc_span(cout) - 1) / acc_span(cout) * acc_span(cout);
     l.acc_copy = acc_copy_floats(tm, cout);
     l.bytes = l.acc + (int)sizeof(float) * ts * l.acc_copy;
     return l;
@@ -113,6 +116,14 @@ __device__ __forceinline__ int acc_slot(int row, int col) {
 template <int COUT>
 __device__ __forceinline__ unsigned acc_slot_bytes(unsigned row, unsigned col) {
     return row * (COUT * 4) + ((col ^ acc_swizzle<COUT>(row)) << 4);
+}
+
+// The same bytes in XOR-linear form: the row's term has its low log2(acc_span) bits from the swizzle alone and a column slot is less
+// than a span, so slot `col` of the row is acc_row_term(row) ^ (col << 4) -- and stays so with a tile offset that is a multiple of
+// the span added to the term.  A lane's column constants are set once per kernel, the term once per item: one XOR per slot.
+template <int COUT>
+__device__ __forceinline__ unsigned acc_row_term(unsigned row) {
+    return row * (COUT * 4) + (acc_swizzle<COUT>(row) << 4);
 }
 
 // -------------------------------------------------------------------------------------------- row range and chunks
@@ -345,6 +356,24 @@ __device__ __forceinline__ void stage_a1(const int *s_list, const int *s_pad, in
     const int ks = v ? (code >> 3) : 0;
     kk = v ? ks : -1;
     // past the end of the work list the (scalar) list pointer selects the block of padding entries: no per-lane select
+    const int *lst = v ? s_list + ks * TM + wr * (TM / WR) + (code & 7) * ITEM : s_pad;
+    e = lst[lp];
+}
+
+// A work list of at most 64 items (the 32-pair kernel's: 32) needs no LDS round trip per item: after build_items lane i holds code i
+// in a register (one read per chunk), and stage A0 is a v_readlane with a scalar lane index: the code arrives in a scalar register.
+template <int SLOT>
+__device__ __forceinline__ int item_codes(const unsigned short *items) {
+    static_assert(SLOT <= 64 && (SLOT & (SLOT - 1)) == 0, "one code per lane");
+    return (int)items[threadIdx.x & (SLOT - 1)];
+}
+__device__ __forceinline__ int stage_a0_reg(int codes, int n_items, int it) { return __builtin_amdgcn_readlane(codes, it < n_items ? it : 0); }
+// stage A1 on a code that is scalar already
+template <int TM, int WR, int ITEM>
+__device__ __forceinline__ void stage_a1_s(const int *s_list, const int *s_pad, int n_items, int wr, int lp, int it, int code, int &kk, int &e) {
+    const bool v = it < n_items;
+    const int ks = v ? (code >> 3) : 0;
+    kk = v ? ks : -1;
     const int *lst = v ? s_list + ks * TM + wr * (TM / WR) + (code & 7) * ITEM : s_pad;
     e = lst[lp];
 }

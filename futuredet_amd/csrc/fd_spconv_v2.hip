@@ -111,6 +111,9 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
     unsigned char *acc_bytes = reinterpret_cast<unsigned char *>(s_acc + ts * L.acc_copy);  // this wave's tile copy
     const unsigned slot0 = (unsigned)(cb >> 2) + (unsigned)lq;  // 16-byte slot of this lane's 4 channels in block nw = 0
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
+    constexpr int kTapBytes = NC * NB * 64 * 16;  // packed weights: [K][NC][NB][64 lanes] float4
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(wp), 0, K * kTapBytes, 0x00020000);
+    const unsigned w_lane = (unsigned)(lane * 16 + wc * NBW * 64 * 16);
     unsigned short *items = s_items + wave * L.item_slot;
 
     for (int chunk = 0; chunk < n_chunks; ++chunk) {
@@ -165,12 +168,16 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
         return SWZ ? __builtin_amdgcn_raw_buffer_load_b128(rsrc, (voff ^ (unsigned)((c & 1) * 64)) + (c >> 1) * 128, 0, 0)
                    : __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + c * 64, 0, 0);
     };
+    // weight fragments through a buffer resource: the lane's part of the address is set once (w_lane), tap and (c, nw) go into the scalar
+    // offset -- a tap switch costs scalar adds, no 64-bit address arithmetic on the vector ALU
+    auto load_w = [&](int k, int c, int nw) {
+        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, w_lane, k * kTapBytes + (c * NB + nw) * 64 * 16, 0));
+    };
     auto load_b = [&](int k, float4(&dst)[NC][NBW]) {
-        const float4 *wk = wp + ((int64_t)k * NC * NB + wc * NBW) * 64 + lane;
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
-            for (int nw = 0; nw < NBW; ++nw) dst[c][nw] = wk[(c * NB + nw) * 64];
+            for (int nw = 0; nw < NBW; ++nw) dst[c][nw] = load_w(k, c, nw);
     };
     // One weight slice in registers.  It is replaced IN PLACE during the last item of a tap: as soon as the MFMAs of a
     // 16-channel chunk have consumed b[c], the same registers are reloaded with the next tap's chunk, so the weights
@@ -252,13 +259,12 @@ __global__ void __launch_bounds__(256) spconv_f32_compact(const float *__restric
             }
             __builtin_amdgcn_sched_barrier(0);
             if (reload) {
-                const float4 *wk = wp + ((int64_t)knext * NC * NB + wc * NBW) * 64 + lane;
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
                     mfma_chunk(a_r[d][c], b[c], acc);
                     if constexpr (kSpread) a_r[dn][c] = gather_chunk(vo, c);  // the gather of item i+DEPTH-1 is spread between the MFMAs
 #pragma unroll
-                    for (int nw = 0; nw < NBW; ++nw) b[c][nw] = wk[(c * NB + nw) * 64];
+                    for (int nw = 0; nw < NBW; ++nw) b[c][nw] = load_w(knext, c, nw);
                     __builtin_amdgcn_sched_group_barrier(0x008, 4 * NBW, 0);
                     __builtin_amdgcn_sched_group_barrier(0x020, (kSpread ? 1 : 0) + NBW, 0);
                 }
