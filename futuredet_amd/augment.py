@@ -25,9 +25,20 @@ cloud pastes their points in front of the scene.  A cloud always grows by ``samp
 is a sentinel row far outside every range, which the voxelisers drop -- so the host knows every size and nothing waits for the device.
 GTSampler's docstring names the two intended differences from the reference.
 
-Everything is opt-in: with ``warp_bev=False`` / ``filter_gt=False`` / ``sampler=None`` the launches are the earlier ones.  In eval mode
+The point-count filter (``min_points_in_gt``, preprocess.py:140-143) and the database itself rest on one primitive, "which points lie
+inside which rotated 3-D boxes" (box_np_ops.points_in_rbbox / points_count_rbbox; fd_points_in_boxes.hip, the header has the arithmetic):
+
+    aug = GlobalAugment(cfg.train_preprocessor, seed=0, point_filter=True)    # accepts min_points_in_gt > 0
+    counts = points_count_rbbox(cloud, boxes)                                 # int32 [n_boxes], on the device
+    rows, offsets = points_in_boxes(cloud, boxes)                             # each box's points, object-centred
+    create_gt_database(samples, "gt_database", "dbinfos_train.pkl")           # the reference's files, from device tensors
+    db = GTDatabase.from_samples(samples, class_names, device="cuda")         # or the database without the files
+
+Everything is opt-in: with ``warp_bev=False`` / ``filter_gt=False`` / ``sampler=None`` / ``point_filter=False`` the launches are the
+earlier ones.  In eval mode
 ``get_mask`` runs with identity parameters, under which the warp returns its input bit for bit, so that path needs no code.  Not
-covered (NotImplementedError where a config asks for it): ``min_points_in_gt``, ``npoints``, per-object rotation noise of the sampler
+covered (NotImplementedError where a config asks for it): ``min_points_in_gt`` without ``point_filter=True``, ``npoints``, per-object
+rotation noise of the sampler
 (``global_random_rotation_range_per_object`` other than [0, 0]) and group sampling; not built: the registered ``Preprocess`` pipeline
 stage, which stays a stub, its name-based class filtering (host-side data preparation), and the reference's global ``np.random``
 stream (every object here draws from a Generator of its own).
@@ -88,8 +99,15 @@ class GlobalAugment(object):
     ``draw(B)`` draws B samples' parameters from the object's own ``numpy.random.Generator`` (``seed``) in the reference's order of
     draws -- the reference's global ``np.random`` stream is not reproduced; ``record(params)`` turns them into the kernels' records;
     ``aug(batch)`` returns an augmented copy of a device batch.  With ``no_augmentation=True`` or a mode other than "train" the
-    transforms are the identity and only the shuffle remains.  ``min_points_in_gt > 0`` and ``npoints > 0`` raise NotImplementedError,
-    and so does an enabled ``db_sampler`` unless a ``sampler`` is given.
+    transforms are the identity and only the shuffle remains.  ``min_points_in_gt > 0`` (unless ``point_filter=True``) and
+    ``npoints > 0`` raise NotImplementedError, and so does an enabled ``db_sampler`` unless a ``sampler`` is given.  (The reference reads
+    ``npoints`` and never uses it; it stays refused so that a config that sets it is noticed.)
+
+    ``point_filter`` (False = as before): accepts ``min_points_in_gt > 0``, the reference's point-count filter (preprocess.py:140-143).
+    As there, it is active (``min_points`` > 0) only in train mode without ``no_augmentation``; ``aug(batch)`` then applies
+    ``filter_gt_by_min_points`` FIRST -- the counts come from the raw cloud and the raw timestep-0 boxes, the same mask goes to every
+    timestep -- before sampling and before the transforms, so sampled entries are appended afterwards and are never filtered.  The
+    static steps do the same while they load a batch.
 
     ``sampler`` (a GTSampler; None = no GT-database sampling, the launches of before): ``aug(batch)`` first samples -- the candidates
     are ``batch["gt_sample_candidates"]`` [B, K] if present, else a draw, and are kept in the returned batch -- so the accepted
@@ -105,8 +123,9 @@ class GlobalAugment(object):
     batch has one, and the static steps draw for such a head and warp the batch's unwarped map themselves.  The map must be
     [B, C, 180, 180] (ValueError otherwise): the reference hard-codes that size and the centre (90, 90)."""
 
-    def __init__(self, cfg, seed=None, warp_bev=False, sampler=None):
+    def __init__(self, cfg, seed=None, warp_bev=False, sampler=None, point_filter=False):
         self.warp_bev = bool(warp_bev)
+        self.point_filter = bool(point_filter)
         self.sampler = sampler
         db = _get(cfg, "db_sampler")
         if db is not None and _get(db, "enable", True):
@@ -114,8 +133,9 @@ class GlobalAugment(object):
                 raise NotImplementedError("GlobalAugment: an enabled db_sampler (GT-database sampling) needs sampler=GTSampler(...); "
                                           "without one, set db_sampler.enable = False")
             check_db_sampler_cfg(db)
-        if _get(cfg, "min_points_in_gt", -1) > 0:
-            raise NotImplementedError("GlobalAugment: min_points_in_gt > 0 (the point-count filter) is not built")
+        min_points = int(_get(cfg, "min_points_in_gt", -1))
+        if min_points > 0 and not self.point_filter:
+            raise NotImplementedError("GlobalAugment: min_points_in_gt > 0 (the point-count filter) needs point_filter=True")
         if _get(cfg, "npoints", -1) > 0:
             raise NotImplementedError("GlobalAugment: npoints > 0 (point sub-sampling) is not built")
         self.shuffle_points = bool(_get(cfg, "shuffle_points", False))
@@ -130,6 +150,7 @@ class GlobalAugment(object):
             raise ValueError("GlobalAugment: global_rot_noise / global_scale_noise take two values, global_translate_std one or three")
         self.rot_noise, self.scale_noise, self.translate_std = [float(v) for v in rot], [float(v) for v in scale], [float(v) for v in std]
         self.sampling = sampler is not None and not self.identity  # (the reference samples inside its train / augmenting branch only)
+        self.min_points = min_points if self.point_filter and min_points > 0 and not self.identity else 0  # 0: the filter is inactive
         self.rng = np.random.default_rng(seed)
         self._perm_dev = collections.OrderedDict()
 
@@ -221,6 +242,8 @@ class GlobalAugment(object):
         transformed below ``gt_counts`` [B, T]; every other entry is passed through, and ``aug_params`` holds the parameters used
         (``params``, else batch["aug_params"], else a fresh draw).  With ``warp_bev`` a ``bev_map`` [B, C, 180, 180] entry is replaced by
         its warped copy."""
+        if self.min_points > 0:  # on the raw cloud and the raw boxes, before everything else
+            batch = filter_gt_by_min_points(batch, self.min_points)
         clouds, boxes = batch["clouds"], batch["gt_boxes"]
         if params is None:
             params = batch.get("aug_params")
@@ -385,6 +408,86 @@ class GTDatabase(object):
         return cls(boxes, steps, classes, traj, np.concatenate(points), offsets, device, class_names=class_names)
 
 
+    @classmethod
+    def from_samples(cls, samples, class_names, device="cuda", num_point_features=None):
+        """The database of ``samples`` without the files: what ``from_dbinfos`` returns for what ``create_gt_database`` writes (all
+        classes of ``class_names``, no prep steps).  One sample is a dict: ``points`` [n, 4 | 5] fp32 (a device tensor or an array),
+        ``boxes`` [T, N, 12], ``names`` (N strings) and ``trajectory`` (N of "static" / "linear" / "nonlinear").  Entries are ordered
+        class after class in the order the classes first appear, as the pickle's dict is."""
+        by_name, class_names = {}, list(class_names)
+        for pts, boxes, names, traj, _ in _database_entries(samples, device, None, num_point_features):
+            for i, p in pts.items():
+                if traj[i] not in _TRAJECTORY:
+                    raise KeyError("%s_%s" % (traj[i], names[i]))
+                by_name.setdefault(names[i], []).append((boxes[:, i], class_names.index(names[i]) + 1 if names[i] in class_names else 0,
+                                                         _TRAJECTORY.index(traj[i]), p))
+        entries = [e for name, lst in by_name.items() if name in class_names for e in lst]
+        if not entries:
+            raise ValueError("GTDatabase.from_samples: no entry of the classes %r" % (class_names,))
+        T = max(len(e[0]) for e in entries)
+        boxes = np.zeros((len(entries), T, 12), np.float32)
+        for k, e in enumerate(entries):
+            boxes[k, :len(e[0])] = e[0]
+        offsets = np.concatenate([[0], np.cumsum([len(e[3]) for e in entries])])
+        return cls(boxes, [len(e[0]) for e in entries], [e[1] for e in entries], [e[2] for e in entries], np.concatenate([e[3] for e in entries]),
+                   offsets, device, class_names=class_names)
+
+
+def _database_entries(samples, device, used_classes, num_point_features):
+    """per sample with objects: (points {object i: fp32 rows, object-centred}, boxes [T, N, 12], names, trajectory, image_idx) -- one
+    points_in_boxes per sample on the device, its rows read back once"""
+    for index, s in enumerate(samples):
+        boxes = np.ascontiguousarray(s["boxes"].cpu().numpy() if isinstance(s["boxes"], torch.Tensor) else s["boxes"], np.float32)
+        if boxes.ndim != 3 or boxes.shape[2] != 12:
+            raise ValueError("a sample's boxes must be [T, N, 12], got %s" % (boxes.shape,))
+        names, traj = [str(v) for v in s["names"]], [str(v) for v in s["trajectory"]]
+        if len(names) != boxes.shape[1] or len(traj) != boxes.shape[1]:
+            raise ValueError("a sample with %d boxes has %d names and %d trajectory types" % (boxes.shape[1], len(names), len(traj)))
+        if boxes.shape[1] == 0:  # (the reference skips a sample without objects)
+            continue
+        pts = s["points"]
+        pts = pts if isinstance(pts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pts, np.float32))
+        pts = pts.to(device=device, dtype=torch.float32).contiguous()
+        ncols = None if num_point_features is None else min(int(num_point_features), int(pts.shape[1]))  # (points[:, :point_features])
+        rows, offsets = points_in_boxes(pts, torch.from_numpy(boxes[0].copy()).to(pts.device), ncols=ncols)
+        rows, offsets = rows.cpu().numpy(), offsets.cpu().numpy()
+        keep = {i: rows[offsets[i]:offsets[i + 1]] for i in range(boxes.shape[1]) if used_classes is None or names[i] in used_classes}
+        yield keep, boxes, names, traj, s.get("image_idx", index)
+
+
+def create_gt_database(samples, db_path, dbinfo_path, used_classes=None, num_point_features=5, relative_path=True, device="cuda"):
+    """The reference's ground-truth database (det3d/datasets/utils/create_gt_database.py:109-176) from ``samples`` (GTDatabase.from_samples
+    names their entries; ``image_idx`` defaults to the sample's position; dataset iteration and sweep loading stay the caller's): per
+    object of a used class the file ``<db_path>/<name>/<image_idx>_<name>_<i>.bin`` -- the first ``num_point_features`` columns of the
+    cloud's points inside the object's timestep-0 box, minus the box centre, fp32 -- and in the pickle ``dbinfo_path`` a dict class name
+    -> entries with ``name`` and ``trajectory`` (one per timestep), ``path`` (relative to db_path's parent, or absolute with
+    ``relative_path=False``), ``image_idx``, ``gt_idx``, ``box3d_lidar`` (the rows of every timestep), ``num_points_in_gt``,
+    ``difficulty`` (zeros) and ``group_id`` (a running number).  Samples without objects are skipped.  Returns the dict.
+    ``GTDatabase.from_dbinfos(dbinfo_path, <db_path's parent>, ...)`` reads it back."""
+    import os
+    import pickle
+
+    db_path = str(db_path)
+    os.makedirs(db_path, exist_ok=True)
+    stem = os.path.splitext(os.path.basename(os.path.normpath(db_path)))[0]  # (Path.stem, as the reference builds the relative path)
+    infos, group = {}, 0
+    for pts, boxes, names, traj, image_idx in _database_entries(samples, device, used_classes, num_point_features):
+        T = boxes.shape[0]
+        for i, p in pts.items():
+            filename = "%s_%s_%d.bin" % (image_idx, names[i], i)
+            os.makedirs(os.path.join(db_path, names[i]), exist_ok=True)
+            filepath = os.path.join(db_path, names[i], filename)
+            np.ascontiguousarray(p, np.float32).tofile(filepath)
+            infos.setdefault(names[i], []).append({
+                "name": [names[i]] * T, "trajectory": [traj[i]] * T, "path": os.path.join(stem, names[i], filename) if relative_path else filepath,
+                "image_idx": image_idx, "gt_idx": i, "box3d_lidar": [boxes[t, i].copy() for t in range(T)], "num_points_in_gt": int(p.shape[0]),
+                "difficulty": [np.int32(0)] * T, "group_id": group})
+            group += 1
+    with open(str(dbinfo_path), "wb") as f:
+        pickle.dump(infos, f)
+    return infos
+
+
 class _BatchSampler(object):
     """The reference's BatchSampler (det3d/core/sampler/preprocess.py:19-54) over n indices: a shuffled list read in slices; a draw
     that would reach the end (``idx + num >= n``) returns what is left -- possibly fewer than asked for -- and reshuffles."""
@@ -513,6 +616,48 @@ def filter_gt_outside_range(batch, pc_range):
     return out
 
 
+def points_count_rbbox(points, boxes, n_boxes=None):
+    """box_np_ops.points_count_rbbox on device tensors: int32 [n_boxes] = the points of ``points`` [n, 4 | 5] inside each row of ``boxes``
+    [n_boxes, >= 7] (the angle is the LAST column).  ``n_boxes``: one int32 on the device, rows at or past it count 0.  Two launches,
+    no synchronisation."""
+    return hip_ops.points_in_boxes_count(points.contiguous(), boxes.contiguous(), n_boxes=n_boxes)[0]
+
+
+def points_in_boxes(points, boxes, ncols=None):
+    """box_np_ops.points_in_rbbox as rows: (rows [total, ncols] fp32, offsets int64 [n_boxes + 1]) -- box j owns the rows
+    offsets[j]..offsets[j + 1], its points in cloud order, columns 0..2 minus the box centre; ``ncols`` (None: all) leading columns.  A
+    point inside two boxes appears under both.  The offline path: the totals are read back once to size ``rows`` exactly."""
+    points, boxes = points.contiguous(), boxes.contiguous()
+    ncols = int(points.shape[1] if ncols is None else ncols)
+    counts, ws = hip_ops.points_in_boxes_count(points, boxes)
+    total = int(counts.sum().item())
+    rows = torch.empty((total, ncols), dtype=torch.float32, device=points.device)
+    rows, offsets, _ = hip_ops.points_in_boxes_extract(points, boxes, ws, rows)
+    return rows, offsets
+
+
+def filter_gt_by_min_points(batch, min_points):
+    """The reference's ``min_points_in_gt`` filter (preprocess.py:140-143) for a device batch: a new batch dict whose ``gt_boxes`` /
+    ``gt_classes`` / ``gt_trajectory`` keep, at every timestep, the objects whose timestep-0 box holds at least ``min_points`` points of
+    the sample's cloud, moved to the front (zeros behind them), with ``gt_counts`` the new counts.  ``gt_point_counts`` [B, n] int32 are
+    the counts, ``gt_min_points_status`` [B] the timesteps of a sample whose count differed from timestep 0's.  Two launches per cloud
+    and one for the batch, no synchronisation."""
+    out = dict(batch)
+    boxes, counts = batch["gt_boxes"].contiguous(), batch["gt_counts"].contiguous()
+    if boxes.shape[2] == 0:
+        return out
+    pc = torch.empty((boxes.shape[0], boxes.shape[2]), dtype=torch.int32, device=boxes.device)
+    for b, c in enumerate(batch["clouds"]):
+        hip_ops.points_in_boxes_count(c.contiguous(), boxes[b, 0], n_boxes=counts[b, 0:1], out=pc[b])
+    traj = batch.get("gt_trajectory")
+    nb, n, c, t, status = hip_ops.gt_min_points_filter(boxes, counts, batch["gt_classes"].contiguous(), pc, int(min_points),
+                                                       trajectory=traj.contiguous() if traj is not None else None)
+    out["gt_boxes"], out["gt_counts"], out["gt_classes"], out["gt_point_counts"], out["gt_min_points_status"] = nb, n, c, pc, status
+    if traj is not None:
+        out["gt_trajectory"] = t
+    return out
+
+
 def bev_range(pc_range):
     """(xmin, ymin, xmax, ymax) of a four- or six-value range (``pc_range[[0, 1, 3, 4]]`` of a voxel range), as fp32 values"""
     r = [float(np.float32(v)) for v in pc_range]
@@ -530,5 +675,5 @@ def identity_params(B):
     return out
 
 
-__all__ = ["GlobalAugment", "GTDatabase", "GTSampler", "check_db_sampler_cfg", "reference_permutation", "identity_params", "filter_gt_outside_range", "bev_range", "check_bev_size",
+__all__ = ["GlobalAugment", "GTDatabase", "GTSampler", "check_db_sampler_cfg", "reference_permutation", "identity_params", "filter_gt_outside_range", "filter_gt_by_min_points", "points_count_rbbox", "points_in_boxes", "create_gt_database", "bev_range", "check_bev_size",
            "RECORD_DTYPE", "MASK_RECORD_DTYPE", "PARAM_FIELDS", "BEV_SIZE"]

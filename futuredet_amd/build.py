@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libfuturedet_hip.so")
-SOURCES = ["fd_error.hip", "fd_voxelize.hip", "fd_index.hip", "fd_spconv.hip", "fd_spconv_v2.hip", "fd_spconv_c32.hip", "fd_spconv_f32r.hip", "fd_spconv_bf16.hip", "fd_spconv_bf16win.hip", "fd_densify.hip", "fd_conv2d.hip", "fd_conv2d_f32.hip", "fd_conv2d_wino.hip", "fd_conv2d_wino_pc.hip", "fd_decode.hip", "fd_sweeps.hip", "fd_pillars.hip", "fd_forecast.hip", "fd_deform_conv.hip", "fd_deform_conv_grad.hip", "fd_spconv_grad.hip", "fd_spconv_grad_bf16.hip", "fd_targets.hip", "fd_pillars_grad.hip", "fd_optim.hip", "fd_loss.hip", "fd_sparse_bn.hip", "fd_dense_bn.hip", "fd_rows.hip", "fd_conv2d_grad_bf16.hip", "fd_head_tail_bf16.hip", "fd_dense_bn_nhwc.hip", "fd_conv2d_strided_grad_bf16.hip", "fd_augment.hip", "fd_augment_map.hip", "fd_gt_sample.hip"]
+SOURCES = ["fd_error.hip", "fd_voxelize.hip", "fd_index.hip", "fd_spconv.hip", "fd_spconv_v2.hip", "fd_spconv_c32.hip", "fd_spconv_f32r.hip", "fd_spconv_bf16.hip", "fd_spconv_bf16win.hip", "fd_densify.hip", "fd_conv2d.hip", "fd_conv2d_f32.hip", "fd_conv2d_wino.hip", "fd_conv2d_wino_pc.hip", "fd_decode.hip", "fd_sweeps.hip", "fd_pillars.hip", "fd_forecast.hip", "fd_deform_conv.hip", "fd_deform_conv_grad.hip", "fd_spconv_grad.hip", "fd_spconv_grad_bf16.hip", "fd_targets.hip", "fd_pillars_grad.hip", "fd_optim.hip", "fd_loss.hip", "fd_sparse_bn.hip", "fd_dense_bn.hip", "fd_rows.hip", "fd_conv2d_grad_bf16.hip", "fd_head_tail_bf16.hip", "fd_dense_bn_nhwc.hip", "fd_conv2d_strided_grad_bf16.hip", "fd_augment.hip", "fd_augment_map.hip", "fd_gt_sample.hip", "fd_points_in_boxes.hip"]
 # geometry / voxel membership follow the reference's operation order: no fma contraction there.
 # -fno-slp-vectorize: the SLP vectoriser turns scalar geometry into packed-fp32 instructions, some with an op_sel swizzle of src1
 # (v_pk_mul_f32 / v_pk_add_f32 ... op_sel:[0,1]) -- a form that returns wrong values in lanes 48-63 on MI355X while bf16 dense-convolution
@@ -27,6 +27,7 @@ EXTRA = {"fd_decode.hip": ["-ffp-contract=off", "-fno-slp-vectorize"], "fd_sweep
          "fd_augment.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
          "fd_augment_map.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
          "fd_gt_sample.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+         "fd_points_in_boxes.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
          "fd_head_tail_bf16.hip": ["-fno-slp-vectorize"]}
 
 

@@ -2,7 +2,9 @@
 // (include/futuredet_hip.h has the contracts, the arithmetic and the reference lines).  Built with -ffp-contract=off: every product and
 // every sum below is one IEEE operation rounded on its own, so every result is bit-defined.
 //
-//   range_filter  one workgroup per sample.  Phase A: the keep flag of every object of timestep 0 and its exclusive prefix sum, in LDS
+//   gt_filter     the range filter and the point-count filter (fd_gt_min_points_filter): one compaction, two keep flags (KeepInRange: the
+//                 corner test; KeepMinPoints: point_counts[b, i] >= min_points).
+//                 One workgroup per sample.  Phase A: the keep flag of every object of timestep 0 and its exclusive prefix sum, in LDS
 //                 (wave ballots, one running total).  Phase B, per timestep: 256 rows at a time, every lane reads its row (box, class,
 //                 trajectory) into registers, a barrier, then the kept rows are written to their prefix position.  A kept row never moves
 //                 backwards and a chunk only writes below its own end, so rows that are still to be read are never overwritten: that is
@@ -54,9 +56,21 @@ __device__ __forceinline__ bool keep_row(const float *row, const Rect &r) {
 
 __device__ __forceinline__ int clamp_count(int c, int n_max) { return c < 0 ? 0 : (c > n_max ? n_max : c); }
 
-__global__ void __launch_bounds__(kFilterThreads) range_filter(const float *boxes, const int *counts, const int *classes, const int *traj,
-                                                               Rect rect, float *boxes_out, int *counts_out, int *classes_out,
-                                                               int *traj_out, int *status, int T, int n_max) {  // outputs may be the inputs
+// the keep flag of object i of sample b (row = its timestep-0 box): the range filter's corner test, the point-count filter's threshold
+struct KeepInRange {
+    Rect rect;
+    __device__ __forceinline__ bool operator()(const float *row, int64_t, int) const { return keep_row(row, rect); }
+};
+struct KeepMinPoints {
+    const int *point_counts;  // [B, n_max]
+    int min_points;
+    __device__ __forceinline__ bool operator()(const float *, int64_t b_n_max, int i) const { return point_counts[b_n_max + i] >= min_points; }
+};
+
+template <typename Keep>
+__global__ void __launch_bounds__(kFilterThreads) gt_filter(const float *boxes, const int *counts, const int *classes, const int *traj,
+                                                            Keep keep_fn, float *boxes_out, int *counts_out, int *classes_out,
+                                                            int *traj_out, int *status, int T, int n_max) {  // outputs may be the inputs
     __shared__ int s_pre[FD_RANGE_FILTER_MAX_N + 1];  // s_pre[i] = kept objects below i; object i is kept iff s_pre[i + 1] != s_pre[i]
     __shared__ int s_wave[kFilterThreads / 64];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -67,7 +81,7 @@ __global__ void __launch_bounds__(kFilterThreads) range_filter(const float *boxe
     int running = 0;
     for (int base = 0; base < n_max; base += kFilterThreads) {
         const int i = base + tid;
-        const bool keep = i < c0 && keep_row(boxes + (bt0 * n_max + i) * 12, rect);
+        const bool keep = i < c0 && keep_fn(boxes + (bt0 * n_max + i) * 12, (int64_t)b * n_max, i);
         const unsigned long long votes = __ballot(keep);
         const int below = __popcll(votes & ((1ull << lane) - 1ull));
         if (lane == 0) s_wave[wave] = __popcll(votes);
@@ -182,35 +196,66 @@ inline bool same_or_disjoint(const void *in, const void *out, size_t bytes) { re
 
 }  // namespace
 
-extern "C" int fd_gt_range_filter(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory, float xmin,
-                                  float ymin, float xmax, float ymax, float *boxes_out, int32_t *counts_out, int32_t *classes_out,
-                                  int32_t *trajectory_out, int32_t *status, int B, int T, int n_max, fd_stream_t stream_) {
-    FD_REQUIRE(B >= 1 && T >= 1, "fd_gt_range_filter: B (%d) and T (%d) must be >= 1", B, T);
-    FD_REQUIRE(n_max >= 1 && n_max <= FD_RANGE_FILTER_MAX_N, "fd_gt_range_filter: n_max (%d) must lie in [1, %d]", n_max, FD_RANGE_FILTER_MAX_N);
-    FD_REQUIRE((int64_t)B * T * n_max <= FD_AUGMENT_MAX_ROWS, "fd_gt_range_filter: B x T x n_max = %lld rows, at most %d", (long long)B * T * n_max,
+// what the two ground-truth filters check alike (``what`` names the entry point); 0 = fine
+static int check_filter_args(const char *what, const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory,
+                             float *boxes_out, int32_t *counts_out, int32_t *classes_out, int32_t *trajectory_out, int32_t *status, int B, int T,
+                             int n_max) {
+    FD_REQUIRE(B >= 1 && T >= 1, "%s: B (%d) and T (%d) must be >= 1", what, B, T);
+    FD_REQUIRE(n_max >= 1 && n_max <= FD_RANGE_FILTER_MAX_N, "%s: n_max (%d) must lie in [1, %d]", what, n_max, FD_RANGE_FILTER_MAX_N);
+    FD_REQUIRE((int64_t)B * T * n_max <= FD_AUGMENT_MAX_ROWS, "%s: B x T x n_max = %lld rows, at most %d", what, (long long)B * T * n_max,
                FD_AUGMENT_MAX_ROWS);
-    FD_REQUIRE(isfinite(xmin) && isfinite(ymin) && isfinite(xmax) && isfinite(ymax) && xmax > xmin && ymax > ymin,
-               "fd_gt_range_filter: the range (%g, %g, %g, %g) must be finite with xmax > xmin and ymax > ymin", xmin, ymin, xmax, ymax);
     FD_REQUIRE(boxes && counts && classes && boxes_out && counts_out && classes_out && status,
-               "fd_gt_range_filter: null boxes, counts, classes, one of their outputs or status");
-    FD_REQUIRE(!trajectory || trajectory_out, "fd_gt_range_filter: a trajectory needs trajectory_out");
-    FD_REQUIRE(aligned(boxes, 16) && aligned(boxes_out, 16), "fd_gt_range_filter: boxes and boxes_out must be 16-byte aligned");
+               "%s: null boxes, counts, classes, one of their outputs or status", what);
+    FD_REQUIRE(!trajectory || trajectory_out, "%s: a trajectory needs trajectory_out", what);
+    FD_REQUIRE(aligned(boxes, 16) && aligned(boxes_out, 16), "%s: boxes and boxes_out must be 16-byte aligned", what);
     FD_REQUIRE(aligned(counts, 4) && aligned(classes, 4) && aligned(trajectory, 4) && aligned(counts_out, 4) && aligned(classes_out, 4) &&
                    aligned(trajectory_out, 4) && aligned(status, 4),
-               "fd_gt_range_filter: the int32 arrays must be 4-byte aligned");
+               "%s: the int32 arrays must be 4-byte aligned", what);
     const size_t sets = (size_t)B * T, rows = sets * n_max;
     FD_REQUIRE(same_or_disjoint(boxes, boxes_out, rows * 48) && same_or_disjoint(counts, counts_out, sets * 4) &&
                    same_or_disjoint(classes, classes_out, rows * 4) && (!trajectory || same_or_disjoint(trajectory, trajectory_out, rows * 4)),
-               "fd_gt_range_filter: an output must be its input itself or not overlap it");
-    Rect r;
+               "%s: an output must be its input itself or not overlap it", what);
+    return FD_OK;
+}
+
+extern "C" int fd_gt_range_filter(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory, float xmin,
+                                  float ymin, float xmax, float ymax, float *boxes_out, int32_t *counts_out, int32_t *classes_out,
+                                  int32_t *trajectory_out, int32_t *status, int B, int T, int n_max, fd_stream_t stream_) {
+    const int rc = check_filter_args("fd_gt_range_filter", boxes, counts, classes, trajectory, boxes_out, counts_out, classes_out, trajectory_out,
+                                     status, B, T, n_max);
+    if (rc != FD_OK) return rc;
+    FD_REQUIRE(isfinite(xmin) && isfinite(ymin) && isfinite(xmax) && isfinite(ymax) && xmax > xmin && ymax > ymin,
+               "fd_gt_range_filter: the range (%g, %g, %g, %g) must be finite with xmax > xmin and ymax > ymin", xmin, ymin, xmax, ymax);
+    KeepInRange keep;
+    Rect &r = keep.rect;
     const float x1 = xmin + (xmax - xmin), y1 = ymin + (ymax - ymin);  // minmax_to_corner_2d: centre + dims, in fp32
     r.px[0] = xmin; r.py[0] = ymin;
     r.px[1] = xmin; r.py[1] = y1;
     r.px[2] = x1;   r.py[2] = y1;
     r.px[3] = x1;   r.py[3] = ymin;
-    hipLaunchKernelGGL(range_filter, dim3((unsigned)B), dim3(kFilterThreads), 0, fd::as_stream(stream_), boxes, counts, classes, trajectory, r,
-                       boxes_out, counts_out, classes_out, trajectory ? trajectory_out : nullptr, status, T, n_max);
+    hipLaunchKernelGGL(gt_filter<KeepInRange>, dim3((unsigned)B), dim3(kFilterThreads), 0, fd::as_stream(stream_), boxes, counts, classes, trajectory,
+                       keep, boxes_out, counts_out, classes_out, trajectory ? trajectory_out : nullptr, status, T, n_max);
     return fd::check_launch("fd_gt_range_filter");
+}
+
+extern "C" int fd_gt_min_points_filter(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory,
+                                       const int32_t *point_counts, int min_points, float *boxes_out, int32_t *counts_out, int32_t *classes_out,
+                                       int32_t *trajectory_out, int32_t *status, int B, int T, int n_max, fd_stream_t stream_) {
+    const int rc = check_filter_args("fd_gt_min_points_filter", boxes, counts, classes, trajectory, boxes_out, counts_out, classes_out,
+                                     trajectory_out, status, B, T, n_max);
+    if (rc != FD_OK) return rc;
+    FD_REQUIRE(point_counts && aligned(point_counts, 4), "fd_gt_min_points_filter: point_counts must be non-null and 4-byte aligned");
+    const size_t sets = (size_t)B * T, rows = sets * n_max, pc = (size_t)B * n_max * 4;
+    FD_REQUIRE(disjoint(point_counts, boxes_out, pc, rows * 48) && disjoint(point_counts, counts_out, pc, sets * 4) &&
+                   disjoint(point_counts, classes_out, pc, rows * 4) && (!trajectory || disjoint(point_counts, trajectory_out, pc, rows * 4)) &&
+                   disjoint(point_counts, status, pc, (size_t)B * 4),
+               "fd_gt_min_points_filter: point_counts must not overlap an output");
+    KeepMinPoints keep;
+    keep.point_counts = point_counts;
+    keep.min_points = min_points;
+    hipLaunchKernelGGL(gt_filter<KeepMinPoints>, dim3((unsigned)B), dim3(kFilterThreads), 0, fd::as_stream(stream_), boxes, counts, classes,
+                       trajectory, keep, boxes_out, counts_out, classes_out, trajectory ? trajectory_out : nullptr, status, T, n_max);
+    return fd::check_launch("fd_gt_min_points_filter");
 }
 
 extern "C" int fd_augment_mask_check(const fd_augment_mask_record *recs_host, int B, int H, int W) {

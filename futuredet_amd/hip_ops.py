@@ -1834,16 +1834,11 @@ def augment_boxes(boxes, counts, recs, out=None):
 AUGMENT_MASK_RECORD_DOUBLES = ctypes.sizeof(_lib.AugmentMaskRecord) // 8  # a mask record travels as 13 float64 words (104 bytes)
 
 
-def gt_range_filter(boxes, counts, classes, pc_range, trajectory=None, out=None, status=None):
-    """fd_gt_range_filter: drops, at every timestep, the objects whose timestep-0 box has no BEV corner strictly inside ``pc_range``
-    (xmin, ymin, xmax, ymax) and moves the kept rows to the front.  boxes [B, T, n_max, 12] fp32, counts [B, T] int32, classes and
-    ``trajectory`` (or None) [B, T, n_max] int32, all on the device.  ``out``: None = new tensors, "inplace" = the inputs themselves, or
-    a tuple (boxes, counts, classes, trajectory | None) of tensors shaped like the inputs (each may be its input).  Rows at or past the
-    new counts are zeros.  ``status`` int32 [B] (None: new) receives the number of timesteps whose count differs from timestep 0's.
-    Returns (boxes, counts, classes, trajectory | None, status).  One launch, no synchronisation."""
+def _gt_filter_inputs(what, boxes, counts, classes, trajectory):
+    """the padded ground truth of the two filters, checked: (ins, names, B, T, n_max)"""
     boxes = _dev(boxes, "boxes", torch.float32)
     if boxes.dim() != 4 or boxes.shape[3] != 12 or min(boxes.shape[:3]) < 1:
-        raise FutureDetHipError("gt_range_filter: boxes must be [B, T, n_max, 12] with B, T, n_max >= 1 (got %s)" % (tuple(boxes.shape),))
+        raise FutureDetHipError("%s: boxes must be [B, T, n_max, 12] with B, T, n_max >= 1 (got %s)" % (what, tuple(boxes.shape),))
     B, T, n_max = (int(v) for v in boxes.shape[:3])
     ins = [boxes, _dev(counts, "counts", torch.int32), _dev(classes, "classes", torch.int32),
            _dev(trajectory, "trajectory", torch.int32) if trajectory is not None else None]
@@ -1851,34 +1846,68 @@ def gt_range_filter(boxes, counts, classes, pc_range, trajectory=None, out=None,
     names = ["boxes", "counts", "classes", "trajectory"]
     for t, shape, name in zip(ins, shapes, names):
         if t is not None and (tuple(t.shape) != shape or t.device != boxes.device):
-            raise FutureDetHipError("gt_range_filter: %s must be %s on %s (got %s on %s)" % (name, list(shape), boxes.device, tuple(t.shape), t.device))
-    rng = [float(v) for v in pc_range]
-    if len(rng) != 4:
-        raise FutureDetHipError("gt_range_filter: pc_range takes (xmin, ymin, xmax, ymax), got %d values" % len(rng))
+            raise FutureDetHipError("%s: %s must be %s on %s (got %s on %s)" % (what, name, list(shape), boxes.device, tuple(t.shape), t.device))
+    return ins, names, B, T, n_max
+
+
+def _gt_filter_outputs(what, ins, names, out, status):
+    """``out`` (None, "inplace" or four tensors) and ``status`` of the two filters, checked: (outs, status)"""
+    boxes, B = ins[0], int(ins[0].shape[0])
     if isinstance(out, str):
         if out != "inplace":
-            raise FutureDetHipError("gt_range_filter: out must be None, \"inplace\" or a tuple of four tensors")
+            raise FutureDetHipError("%s: out must be None, \"inplace\" or a tuple of four tensors" % what)
         outs = list(ins)
     elif out is None:
         outs = [torch.empty_like(t) if t is not None else None for t in ins]
     else:
         outs = list(out)
         if len(outs) != 4:
-            raise FutureDetHipError("gt_range_filter: out takes (boxes, counts, classes, trajectory | None)")
+            raise FutureDetHipError("%s: out takes (boxes, counts, classes, trajectory | None)" % what)
         for i, (t, src, name) in enumerate(zip(outs, ins, names)):
             if src is None:
                 outs[i] = None
                 continue
             t = _dev(t, name + "_out", src.dtype)
             if tuple(t.shape) != tuple(src.shape) or t.device != src.device:
-                raise FutureDetHipError("gt_range_filter: %s_out %s does not match %s %s" % (name, tuple(t.shape), name, tuple(src.shape)))
+                raise FutureDetHipError("%s: %s_out %s does not match %s %s" % (what, name, tuple(t.shape), name, tuple(src.shape)))
     if status is None:
         status = torch.empty((B,), dtype=torch.int32, device=boxes.device)
     status = _dev(status, "status", torch.int32)
     if status.numel() != B or status.device != boxes.device:
-        raise FutureDetHipError("gt_range_filter: status must be int32 [%d] on %s (got %s)" % (B, boxes.device, tuple(status.shape)))
+        raise FutureDetHipError("%s: status must be int32 [%d] on %s (got %s)" % (what, B, boxes.device, tuple(status.shape)))
+    return outs, status
+
+
+def gt_range_filter(boxes, counts, classes, pc_range, trajectory=None, out=None, status=None):
+    """fd_gt_range_filter: drops, at every timestep, the objects whose timestep-0 box has no BEV corner strictly inside ``pc_range``
+    (xmin, ymin, xmax, ymax) and moves the kept rows to the front.  boxes [B, T, n_max, 12] fp32, counts [B, T] int32, classes and
+    ``trajectory`` (or None) [B, T, n_max] int32, all on the device.  ``out``: None = new tensors, "inplace" = the inputs themselves, or
+    a tuple (boxes, counts, classes, trajectory | None) of tensors shaped like the inputs (each may be its input).  Rows at or past the
+    new counts are zeros.  ``status`` int32 [B] (None: new) receives the number of timesteps whose count differs from timestep 0's.
+    Returns (boxes, counts, classes, trajectory | None, status).  One launch, no synchronisation."""
+    ins, names, B, T, n_max = _gt_filter_inputs("gt_range_filter", boxes, counts, classes, trajectory)
+    rng = [float(v) for v in pc_range]
+    if len(rng) != 4:
+        raise FutureDetHipError("gt_range_filter: pc_range takes (xmin, ymin, xmax, ymax), got %d values" % len(rng))
+    outs, status = _gt_filter_outputs("gt_range_filter", ins, names, out, status)
     check(_lib.load().fd_gt_range_filter(_p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), rng[0], rng[1], rng[2], rng[3], _p(outs[0]), _p(outs[1]),
                                          _p(outs[2]), _p(outs[3]), _p(status), B, T, n_max, _stream()), "fd_gt_range_filter")
+    return outs[0], outs[1], outs[2], outs[3], status
+
+
+def gt_min_points_filter(boxes, counts, classes, point_counts, min_points, trajectory=None, out=None, status=None):
+    """fd_gt_min_points_filter: gt_range_filter with another mask -- object i of sample b is kept, at every timestep, iff
+    ``point_counts[b, i] >= min_points``; point_counts int32 [B, n_max] on the device (points_in_boxes_count of the sample's cloud and its
+    timestep-0 boxes), never an output.  Arguments, ``out``, ``status`` and the return value as for gt_range_filter.  One launch, no
+    synchronisation."""
+    ins, names, B, T, n_max = _gt_filter_inputs("gt_min_points_filter", boxes, counts, classes, trajectory)
+    point_counts = _dev(point_counts, "point_counts", torch.int32)
+    if tuple(point_counts.shape) != (B, n_max) or point_counts.device != ins[0].device:
+        raise FutureDetHipError("gt_min_points_filter: point_counts must be int32 [%d, %d] on %s (got %s on %s)"
+                                % (B, n_max, ins[0].device, tuple(point_counts.shape), point_counts.device))
+    outs, status = _gt_filter_outputs("gt_min_points_filter", ins, names, out, status)
+    check(_lib.load().fd_gt_min_points_filter(_p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), _p(point_counts), int(min_points), _p(outs[0]),
+                                              _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(status), B, T, n_max, _stream()), "fd_gt_min_points_filter")
     return outs[0], outs[1], outs[2], outs[3], status
 
 
@@ -2035,6 +2064,77 @@ def gt_sample_points(db, cand, accepted, plan, dst, point_cap):
                                           _p(accepted), _p(plan), K, _p(dst), point_cap, _stream()), "fd_gt_sample_points")
     return dst
 
+
+
+# ---- training: points in rotated boxes (fd_points_in_boxes.hip) -------------------------------------------------------------------
+POINTS_IN_BOXES_NO_ROOM = 1   # FD_POINTS_IN_BOXES_NO_ROOM
+POINTS_IN_BOXES_MAX_N = 4096  # FD_RANGE_FILTER_MAX_N: the boxes of one call
+
+
+def _points_in_boxes_inputs(what, points, boxes, n_boxes):
+    points, boxes = _dev(points, "points", torch.float32), _dev(boxes, "boxes", torch.float32)
+    if points.dim() != 2 or points.shape[1] not in (4, 5):
+        raise FutureDetHipError("%s: points must be [n, 4] or [n, 5] (got %s)" % (what, tuple(points.shape)))
+    if boxes.dim() != 2 or boxes.shape[1] < 7 or boxes.shape[0] > POINTS_IN_BOXES_MAX_N:
+        raise FutureDetHipError("%s: boxes must be [n_boxes <= %d, >= 7] (got %s)" % (what, POINTS_IN_BOXES_MAX_N, tuple(boxes.shape)))
+    if boxes.device != points.device:
+        raise FutureDetHipError("%s: points live on %s, boxes on %s" % (what, points.device, boxes.device))
+    if n_boxes is not None:
+        n_boxes = _dev(n_boxes, "n_boxes", torch.int32)
+        if n_boxes.numel() != 1 or n_boxes.device != points.device:
+            raise FutureDetHipError("%s: n_boxes must be ONE int32 on %s (got %s on %s)" % (what, points.device, tuple(n_boxes.shape), n_boxes.device))
+    return points, boxes, n_boxes
+
+
+def points_in_boxes_workspace(n_points, n_boxes_max, device):
+    """a new uint8 tensor of fd_points_in_boxes_workspace_bytes(n_points, n_boxes_max) bytes (at least 4) for the two calls below"""
+    return torch.empty((max(int(_lib.load().fd_points_in_boxes_workspace_bytes(int(n_points), int(n_boxes_max))), 4),), dtype=torch.uint8, device=device)
+
+
+def points_in_boxes_count(points, boxes, n_boxes=None, out=None, workspace=None):
+    """fd_points_in_boxes_count: int32 [n_boxes_max] = the points of ``points`` [n, 4 | 5] inside each row of ``boxes`` [n_boxes_max, >= 7]
+    (centre, dims, ..., the angle in the LAST column); ``n_boxes``: one int32 on the device, the rows at or past it are no boxes (count
+    0).  ``out`` int32 [n_boxes_max] and ``workspace`` (uint8, points_in_boxes_workspace) let a step keep static buffers; None = new
+    tensors.  Returns (counts, workspace): the workspace is what points_in_boxes_extract reads.  Two launches, no synchronisation."""
+    points, boxes, n_boxes = _points_in_boxes_inputs("points_in_boxes_count", points, boxes, n_boxes)
+    n, m = int(points.shape[0]), int(boxes.shape[0])
+    if out is None:
+        out = torch.empty((m,), dtype=torch.int32, device=points.device)
+    out = _dev(out, "out", torch.int32)
+    if tuple(out.shape) != (m,) or out.device != points.device:
+        raise FutureDetHipError("points_in_boxes_count: out must be int32 [%d] on %s (got %s on %s)" % (m, points.device, tuple(out.shape), out.device))
+    if workspace is None:
+        workspace = points_in_boxes_workspace(n, m, points.device)
+    workspace = _dev(workspace, "workspace", torch.uint8)
+    check(_lib.load().fd_points_in_boxes_count(_p(points), n, int(points.shape[1]), _p(boxes), m, int(boxes.shape[1]), _p(n_boxes), _p(out),
+                                               _p(workspace), workspace.numel(), _stream()), "fd_points_in_boxes_count")
+    return out, workspace
+
+
+def points_in_boxes_extract(points, boxes, workspace, rows, n_boxes=None, offsets=None, status=None):
+    """fd_points_in_boxes_extract on the inputs and the workspace of a points_in_boxes_count call: fills ``rows`` [cap_rows, ncols <= ndim]
+    fp32 box after box with each box's points in their cloud order, columns 0..2 minus the box centre, and ``offsets`` int64
+    [n_boxes_max + 1] (None: new); ``status`` int32 [1] (None: new) gets POINTS_IN_BOXES_NO_ROOM when rows is too short (the rows that
+    fit are written).  Returns (rows, offsets, status).  One launch, no synchronisation."""
+    points, boxes, n_boxes = _points_in_boxes_inputs("points_in_boxes_extract", points, boxes, n_boxes)
+    n, m, dev = int(points.shape[0]), int(boxes.shape[0]), points.device
+    workspace, rows = _dev(workspace, "workspace", torch.uint8), _dev(rows, "rows", torch.float32)
+    if rows.dim() != 2 or not 1 <= rows.shape[1] <= points.shape[1] or rows.device != dev:
+        raise FutureDetHipError("points_in_boxes_extract: rows must be [cap_rows, 1..%d] on %s (got %s on %s)"
+                                % (points.shape[1], dev, tuple(rows.shape), rows.device))
+    if offsets is None:
+        offsets = torch.empty((m + 1,), dtype=torch.int64, device=dev)
+    offsets = _dev(offsets, "offsets", torch.int64)
+    if status is None:
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+    status = _dev(status, "status", torch.int32)
+    if tuple(offsets.shape) != (m + 1,) or status.numel() != 1 or offsets.device != dev or status.device != dev:
+        raise FutureDetHipError("points_in_boxes_extract: offsets must be int64 [%d] and status int32 [1] on %s (got %s, %s)"
+                                % (m + 1, dev, tuple(offsets.shape), tuple(status.shape)))
+    check(_lib.load().fd_points_in_boxes_extract(_p(points), n, int(points.shape[1]), _p(boxes), m, int(boxes.shape[1]), _p(n_boxes), _p(workspace),
+                                                 workspace.numel(), _p(rows) if rows.shape[0] else None, int(rows.shape[0]), int(rows.shape[1]),
+                                                 _p(offsets), _p(status), _stream()), "fd_points_in_boxes_extract")
+    return rows, offsets, status
 
 # ---- training: the fused CenterHead loss (fd_loss.hip) ----------------------------------------------------------------------------
 LOSS_MAPS = ("reg", "height", "dim", "vel", "rvel", "rot", "rrot")  # fd_loss_task.maps / d_maps, in this order

@@ -260,6 +260,12 @@ SIGNATURES = {
                             + [c_int, c_int, c_int, c_int, c_void_p]),
     "fd_gt_sample_points": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                     c_void_p]),
+    "fd_points_in_boxes_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    "fd_points_in_boxes_count": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fd_points_in_boxes_extract": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_i64, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
+    "fd_gt_min_points_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_void_p]),
     "fd_loss_chunk": (c_int, []),
     "fd_centerhead_loss_terms": (c_size_t, [ctypes.POINTER(LossCfg)]),
     "fd_centerhead_loss_workspace_bytes": (c_size_t, [ctypes.POINTER(LossCfg), c_int]),

@@ -414,6 +414,13 @@ class _StaticTrainBase(object):
                                   status=torch.zeros((B,), **i32), groups=hip_ops.gt_sample_groups(s.records),
                                   stage=torch.zeros((B, s.point_cap + self.capacity, self.ndim), dtype=torch.float32, device=dev))
         self.last_gt_sample_candidates = None
+        # augment.min_points > 0 (GlobalAugment(..., point_filter=True) on a cfg with min_points_in_gt): the point-count filter while the
+        # batch is loaded -- the counts of every cloud's raw timestep-0 boxes, the filter's report, and the workspace of
+        # fd_points_in_boxes_count (sized for a cloud of ``capacity`` rows and ``max_gt`` boxes when the first batch is loaded, i.e. at warm_up)
+        self.point_filter = None
+        if int(getattr(augment, "min_points", 0) or 0) > 0:
+            self.point_filter = dict(min_points=int(augment.min_points), counts=torch.zeros((B, n), dtype=torch.int32, device=dev),
+                                     status=torch.zeros((B,), dtype=torch.int32, device=dev), workspace=None)
         self._ring, self._slot = None, 0
         self.iteration = 0
         self.outputs, self.level_counts = None, None
@@ -537,22 +544,33 @@ class _StaticTrainBase(object):
                 self.bev.copy_(batch["bev_map"], non_blocking=True)
 
     def _load_gt(self, batch):
-        """the padded ground truth into the static buffers: copy, (GT-database sampling,) augmentation, (range filter)"""
-        aug, gs = self.augment, getattr(self, "gt_sample", None)
+        """the padded ground truth into the static buffers: copy, (point-count filter,) (GT-database sampling,) augmentation, (range
+        filter)"""
+        aug, gs, pf = self.augment, getattr(self, "gt_sample", None), getattr(self, "point_filter", None)
         boxes, gcounts, classes = batch["gt_boxes"], batch["gt_counts"], batch["gt_classes"]
         n = int(boxes.shape[2])
         if tuple(boxes.shape[:2]) != (self.B, self.T) or n > self.max_gt or boxes.shape[3] != 12:
             raise ValueError("gt_boxes %s do not fit the step's [%d, %d, <= %d, 12] buffer" % (tuple(boxes.shape), self.B, self.T, self.max_gt))
-        if gs is not None:  # copy -> select in place (the step's counts from here on) -> transform -> filter
+        if gs is not None or pf is not None:  # copy -> filter by points, select: in place (the step's counts from here on) -> transform -> filter
             self.gt_boxes[:, :, :n].copy_(boxes, non_blocking=True)
-            self.gt_counts.copy_(gcounts, non_blocking=True)
+            if pf is None:
+                self.gt_counts.copy_(gcounts, non_blocking=True)
             self.gt_classes[:, :, :n].copy_(classes, non_blocking=True)
             if self.gt_trajectory is not None:
                 self.gt_trajectory[:, :, :n].copy_(batch["gt_trajectory"], non_blocking=True)
-            s = aug.sampler
-            hip_ops.gt_sample_select(self.gt_boxes, self.gt_counts, self.gt_classes, s.database, gs["cand"], gs["groups"], s.rate, s.point_cap,
-                                     trajectory=self.gt_trajectory, out="inplace", accepted=gs["accepted"], plan=gs["plan"],
-                                     n_points=gs["n_points"], status=gs["status"])
+            if pf is not None:  # the counts: every RAW cloud against its raw timestep-0 boxes, below the batch's device count
+                if pf["workspace"] is None:
+                    pf["workspace"] = hip_ops.points_in_boxes_workspace(self.capacity, self.max_gt, self.device)
+                raw, gc = boxes.contiguous(), gcounts.contiguous()
+                for b, c in enumerate(batch["clouds"]):
+                    hip_ops.points_in_boxes_count(c, raw[b, 0], n_boxes=gc[b, 0:1], out=pf["counts"][b, :n], workspace=pf["workspace"])
+                hip_ops.gt_min_points_filter(self.gt_boxes, gc, self.gt_classes, pf["counts"], pf["min_points"], trajectory=self.gt_trajectory,
+                                             out=(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_trajectory), status=pf["status"])
+            if gs is not None:
+                s = aug.sampler
+                hip_ops.gt_sample_select(self.gt_boxes, self.gt_counts, self.gt_classes, s.database, gs["cand"], gs["groups"], s.rate, s.point_cap,
+                                         trajectory=self.gt_trajectory, out="inplace", accepted=gs["accepted"], plan=gs["plan"],
+                                         n_points=gs["n_points"], status=gs["status"])
             hip_ops.augment_boxes(self.gt_boxes, self.gt_counts, self.aug_rec, out=self.gt_boxes)
             if getattr(self, "filter_gt", False):
                 hip_ops.gt_range_filter(self.gt_boxes, self.gt_counts, self.gt_classes, self.gt_range, trajectory=self.gt_trajectory,
@@ -682,6 +700,13 @@ class StaticTrainStep(_StaticTrainBase):
     a stage of [B, point_cap + capacity, ndim] (fd_gt_sample_points, a copy) and goes through one fd_augment_points over
     n + point_cap rows, so the cloud counts stay host-known.  A cloud with n + point_cap > capacity raises ValueError before anything
     of the step changes.  ``gt_sample["accepted"]`` [B, K], ``["n_points"]`` and ``["status"]`` [B] hold the kernel's reports.
+
+    The point-count filter (``augment=GlobalAugment(..., point_filter=True)`` on a cfg with ``min_points_in_gt > 0``; inactive = today's
+    launches and buffers): while the ground truth is loaded, one fd_points_in_boxes_count per cloud -- the batch's RAW cloud against its
+    raw timestep-0 boxes, below the batch's device count -- fills ``point_filter["counts"]`` [B, max_gt], and one
+    fd_gt_min_points_filter for the batch drops, at every timestep, the objects with fewer points, in place on the static ground
+    truth, before the sampler's selection and before the transforms: what ``aug(batch)`` does.  ``point_filter["status"]`` [B] counts
+    the timesteps of a sample whose count differed from timestep 0's.  No host synchronisation.
 
     ``graph``: only False.  Everything in the step is capturable by construction (static shapes, device counts, device scalars, a
     device-side overflow guard, nothing keyed on the weights' version), but capturing it -- MIOpen's convolutions and their backward

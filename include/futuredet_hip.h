@@ -1006,6 +1006,64 @@ int fd_gt_sample_points(const float *db_points, int64_t P, int ndim, const float
                         const int32_t *accepted, const fd_gt_sample_plan *plan, int K, float *dst, int point_cap, fd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Training: which points of a cloud lie inside which rotated 3-D boxes (fd_points_in_boxes.hip) -- box_np_ops.points_in_rbbox and
+ * points_count_rbbox (det3d/core/bbox/box_np_ops.py:641-647, 15-20: center_to_corner_box3d -> corner_to_surfaces_3d ->
+ * geometry.surface_equ_3d_jitv2 and points_in_convex_polygon_3d_jit, det3d/core/bbox/geometry.py:215-276, 352-378), what the reference's
+ * ``min_points_in_gt`` filter (det3d/datasets/pipelines/preprocess.py:140-143) and its ground-truth database writer
+ * (det3d/datasets/utils/create_gt_database.py:125-169) are built on.  Purely additive: fd_abi_version() stays 8.  Graph-capturable, no
+ * atomics, no allocation, no synchronisation; every argument is checked on the host before any device work.
+ *
+ * The arithmetic.  Every operation below is one fp32 IEEE operation rounded on its own unless said otherwise.
+ *   A box row has box_cols >= 7 columns: the centre = columns 0, 1, 2; (w, l, h) = columns 3, 4, 5; the angle a = the LAST column, as
+ *     the reference reads it (rbbox[:, -1]: column 11 of our 12-column rows, not column 10); s = fl32(sin(double(a))),
+ *     c = fl32(cos(double(a))) (the reference takes NumPy's fp32 sin / cos, which lie within 1.5 ulp of these).
+ *   Corner k = 0..7 has the unit offsets (bx, by, bz) = (0,0,0), (0,0,1), (0,1,1), (0,1,0), (1,0,0), (1,0,1), (1,1,1), (1,1,0); with
+ *     ox = w (bx - 0.5), oy = l (by - 0.5), oz = h (bz - 0.5):  x_k = (ox c + oy s) + cx,  y_k = (-(ox s) + oy c) + cy,  z_k = oz + cz.
+ *   Face f = 0..5 uses the corners (P0, P1, P2) = (0,1,2), (7,6,5), (0,3,7), (1,5,6), (0,4,5), (3,2,6); with u = P0 - P1, v = P1 - P2:
+ *     n = (u.y v.z - u.z v.y,  u.z v.x - u.x v.z,  u.x v.y - u.y v.x),  d = ((-(P0.x n.x)) - P0.y n.y) - P0.z n.z.
+ *   A point p is INSIDE iff for all six faces ((p.x n.x + p.y n.y) + p.z n.z) + d is NOT >= 0: a point on a face is outside, a NaN
+ *     counts as inside (as in the reference), a box whose three dimensions are zero holds no finite point (n = 0 and d = 0 on every
+ *     face, and 0 >= 0).
+ *
+ * points [n, ndim] fp32, ndim 4 or 5; boxes [n_boxes_max, box_cols] fp32; n_boxes_dev: NULL, or one int32 in device memory -- the rows
+ *   at or past nb = clamp(*n_boxes_dev, 0, n_boxes_max) are never read as boxes and hold no point.  workspace: device memory of
+ *   fd_points_in_boxes_workspace_bytes(n, n_boxes_max) bytes, 4-byte aligned (0 bytes for invalid sizes).
+ * fd_points_in_boxes_count: counts [n_boxes_max] int32 = the points inside each box.  Two launches: the partial counts of every
+ *   (workgroup of 256 points, box) -- box planes in LDS, FD_POINTS_IN_BOXES_TILE boxes at a time whatever n_boxes_max is, one wave
+ *   ballot + popcount per box -- then one pass that sums them per box and leaves their exclusive scan over the workgroups, and the
+ *   totals, in the workspace.  n = 0 writes zeros; n_boxes_max = 0 is a no-op.
+ * fd_points_in_boxes_extract: one more launch, on the SAME inputs and the workspace fd_points_in_boxes_count filled for them.
+ *   offsets [n_boxes_max + 1] int64: offsets[j] = the points in the boxes before j, offsets[n_boxes_max] = the total.  rows
+ *   [cap_rows, ncols_out] fp32, 1 <= ncols_out <= ndim: box after box, each box's points in their cloud order -- row offsets[j] + r is
+ *   the r-th point of the cloud that lies inside box j, columns 0..2 minus the box centre (one fp32 subtraction each), the other
+ *   columns copied bit for bit.  A point inside two boxes appears under both.  A row at or past cap_rows is not written and sets
+ *   FD_POINTS_IN_BOXES_NO_ROOM in status[0] (0 otherwise); rows at or past the total are not written.  The order comes from the scan
+ *   and ballot ranks: two runs write the same bytes.  With a workspace that was not filled for these inputs the result is undefined,
+ *   but nothing is written outside rows [0, cap_rows).
+ *   FD_EINVAL (both) for: ndim not 4 or 5, n outside [0, FD_AUGMENT_MAX_ROWS], n_boxes_max outside [0, FD_RANGE_FILTER_MAX_N],
+ *   box_cols outside [7, FD_POINTS_IN_BOXES_MAX_COLS], a null (for a non-empty array) or misaligned pointer (offsets 8 bytes, the
+ *   others 4), a workspace that is too small, outputs or workspace overlapping one another or an input; extract also: ncols_out outside
+ *   [1, ndim], cap_rows outside [0, FD_AUGMENT_MAX_ROWS].
+ *
+ * fd_gt_min_points_filter (fd_augment_map.hip): fd_gt_range_filter with another mask -- the same arguments but the range, the same
+ *   outputs, padding rule, in-place rule and status.  Object i < c0 of sample b is KEPT iff point_counts[b, i] >= min_points;
+ *   point_counts [B, n_max] int32 in device memory (fd_points_in_boxes_count of the sample's cloud and its timestep-0 boxes) must not
+ *   overlap an output.  FD_EINVAL as for fd_gt_range_filter (without the range), and for a null, misaligned or overlapping point_counts.
+ * ------------------------------------------------------------------------------------------------- */
+#define FD_POINTS_IN_BOXES_TILE 64
+#define FD_POINTS_IN_BOXES_MAX_COLS 64
+#define FD_POINTS_IN_BOXES_NO_ROOM 1
+size_t fd_points_in_boxes_workspace_bytes(int64_t n_points, int n_boxes_max);
+int fd_points_in_boxes_count(const float *points, int64_t n, int ndim, const float *boxes, int n_boxes_max, int box_cols,
+                             const int32_t *n_boxes_dev, int32_t *counts, void *workspace, size_t workspace_bytes, fd_stream_t stream);
+int fd_points_in_boxes_extract(const float *points, int64_t n, int ndim, const float *boxes, int n_boxes_max, int box_cols,
+                               const int32_t *n_boxes_dev, const void *workspace, size_t workspace_bytes, float *rows, int64_t cap_rows,
+                               int ncols_out, int64_t *offsets, int32_t *status, fd_stream_t stream);
+int fd_gt_min_points_filter(const float *boxes, const int32_t *counts, const int32_t *classes, const int32_t *trajectory,
+                            const int32_t *point_counts, int min_points, float *boxes_out, int32_t *counts_out, int32_t *classes_out,
+                            int32_t *trajectory_out, int32_t *status, int B, int T, int n_max, fd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training: CenterHead.loss for the standard and dense heads (fd_loss.hip) -- FastFocalLoss + RegLoss of
  * det3d/models/losses/centernet_loss.py as center_head.py:396-539 combines them, forward terms and the gradient of every head map.
  * Purely additive: fd_abi_version() stays 8.  fp32 maps, contiguous [B, channels, H, W].
